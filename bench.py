@@ -17,15 +17,30 @@ ranks (lib/graph_model.py:296-298 is where the exchange sits in the reference).
 
 The timed loop issues exactly those C-ABI calls on torch's current stream
 (ctypes, pre-bound arguments, no per-step allocation or event), bracketed by
-barrier + synchronize; the max over ranks is reported.  After it, each kernel
-is timed alone in bursts of back-to-back launches with HIP events recorded on
-the same stream (roofline.achieved; the same bursts also run once before the
-warmup to lift the GPU out of its idle clocks); rocprofv3 summaries of the
-same command live under profiles/ (scripts/prof_pmc.sh), whose PMC-measured HBM bytes of
-the dominant kernel are reported as roofline.traffic when they match this
-configuration.
+barrier + synchronize; the max over ranks is reported.  A plain run does no
+more than that: set up, a short burst of forward / backward launches that lifts
+the GPU out of its idle clocks, W warm-up steps, the K timed steps, the
+--dump-outputs files if asked for, and the result line (metric, value, unit,
+ms_per_step, higher_is_better, dtype and the configuration).
+
+--full adds everything else the benchmark measures, after the timed region: a
+second, event-bracketed pass of the same steps (step_ms_median / step_ms_p90),
+each kernel timed alone in bursts of back-to-back launches with HIP events
+recorded on the same stream (roofline.achieved, kernels, contraction_mfma), the
+PMC-measured HBM bytes of the dominant kernel from the rocprofv3 summaries under
+profiles/ (scripts/prof_pmc.sh; roofline.traffic, when they match this
+configuration) and the CPU baseline (the oracle timed on the same workload;
+--no-cpu-baseline leaves it out).
+
+--dump-outputs DIR writes what the last timed step computed -- the arrays a
+caller of the step receives -- as DIR/<name>.npy (float32, rank 0's shard),
+at most 64 MB in all: an array that does not fit is written as a fixed, seeded
+sample of its elements.  Every input (x, dy, W, the labels and the dropout
+masks of config E) is drawn from seeded generators, so two runs with the same
+arguments see identical inputs and their files can be compared one to one.
 
 Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--global-batch G]
+                        [--full] [--dump-outputs DIR]
   N > 1 under torchrun (python -m torch.distributed.run --nproc-per-node N ...
   bench.py --gpus N): one rank per GPU, WORLD_SIZE must equal N.  N > 1
   without torchrun: bench.py starts that torchrun itself as a child process
@@ -270,6 +285,44 @@ def burst_ms(fn, reps=50, rounds=5):
     return float(np.median(vals))
 
 
+DUMP_BYTES = 64 * 1000 * 1000   # --dump-outputs: all files together stay below this
+
+
+def dump_plan(sizes, limit_bytes=DUMP_BYTES):
+    """Elements to write of each array ({name: numel} -> {name: count}) so that
+    the float32 files together stay within `limit_bytes` (256 bytes set aside
+    for each .npy header): the arrays are served smallest first, each taking at
+    most an equal share of what is left, so small arrays are written whole and
+    only the ones that cannot fit are sampled."""
+    plan, left = {}, max(0, limit_bytes // 4 - 64 * len(sizes))
+    order = sorted(sizes, key=lambda k: (sizes[k], k))
+    for i, name in enumerate(order):
+        plan[name] = min(sizes[name], left // (len(order) - i))
+        left -= plan[name]
+    return plan
+
+
+def dump_outputs(dirname, arrays, limit_bytes=DUMP_BYTES):
+    """Write {name: tensor} as dirname/<name>.npy in float32 (the copy to the
+    host waits for the steps enqueued before it).  An array over its share of
+    the 64 MB (dump_plan) is written as a 1-D sample: the elements at sorted
+    flat indices drawn once from a CPU generator seeded with the array's size,
+    the same in every run and every build."""
+    os.makedirs(dirname, exist_ok=True)
+    plan = dump_plan({k: t.numel() for k, t in arrays.items()}, limit_bytes)
+    for name, t in arrays.items():
+        n, flat = plan[name], t.detach().reshape(-1)
+        if n < flat.numel():
+            gen = torch.Generator()
+            gen.manual_seed(flat.numel())
+            idx = torch.randint(flat.numel(), (n,), generator=gen).sort().values
+            flat = flat[idx.to(flat.device)]
+            a = flat.float().cpu().numpy()
+        else:
+            a = t.detach().float().cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def pmc_traffic(kernel, cfg):
     """HBM bytes per launch of `kernel` from the committed rocprofv3 PMC summary
     (scripts/prof_pmc.sh -> profiles/pmc_latest.json) if it was taken on this
@@ -400,7 +453,7 @@ def train_step_d(args, N, world, local, dev, comm, rank):
         x.copy_(torch.rand(x.shape, device=dev, generator=g))
     else:
         x = torch.rand((N, plan.M, Fin), device=dev, generator=g)
-    W = truncated_normal_(torch.empty((Fin * K, Fout), device=dev), 0.1)
+    W = truncated_normal_(torch.empty((Fin * K, Fout), device=dev), 0.1, weight_generator(dev))
     cdist.broadcast_parameters([W])
     dy = torch.randn((N, plan.M, Fout), device=dev, generator=g)
     allreduce = None
@@ -428,7 +481,12 @@ def train_step_d(args, N, world, local, dev, comm, rank):
             "grad_bucket_bytes": 4 * Fin * K * Fout, "adam": "cg_adam_update"}
     cpu = lambda: cpu_baseline_filter("D", Lt, 1, N, Fin, K, Fout, seconds=args.cpu_seconds,  # noqa: E731
                                       warmup=1, min_passes=3)
-    return step, info, kernels, cpu, "bytes"
+
+    def outputs():
+        return {"y": runner.y, "dx": runner.dx, "dW": runner.dW, "W": trainer.W[0],
+                "adam_m": trainer.m[0], "adam_v": trainer.v[0]}
+
+    return step, info, kernels, cpu, "bytes", outputs
 
 
 def train_step_e(args, N, world, local, dev, comm, rank):
@@ -472,7 +530,12 @@ def train_step_e(args, N, world, local, dev, comm, rank):
             "M": M, "T": T, "K": K, "Fin": Fin, "H": H, "Fout": Fout,
             "grad_bucket_bytes": 4 * model.flat.numel(), "adam": "cg_adam_update (flat buffer)"}
     cpu = lambda: cpu_baseline_lstm(Lt, 8, N, T, Fin, H, K, seconds=args.cpu_seconds)  # noqa: E731
-    return step, info, kernels, cpu, "flops"
+
+    def outputs():
+        return {"loss": model.loss, "loss_average": model.loss_average, "grad": model.grad,
+                "params": model.flat}
+
+    return step, info, kernels, cpu, "flops", outputs
 
 
 def run_config_de(args, rank, world, local, dev, json_fd):
@@ -482,13 +545,44 @@ def run_config_de(args, rank, world, local, dev, json_fd):
     N, N_global, strong = batch_split(args, rank, world)
     comm, rccl_nranks = make_exchange(args, world, local)
     build = train_step_d if args.config == "D" else train_step_e
-    step, info, kernels, cpu, bound = build(args, N, world, local, dev, comm, rank)
+    step, info, kernels, cpu, bound, outputs = build(args, N, world, local, dev, comm, rank)
     try:
         elapsed = timed_region(step, args.steps, args.warmup, world, dev)
     except Exception:
         if isinstance(comm, cdist.RcclComm) and comm.async_error(abort=True):
             sys.exit(f"bench.py: RCCL asynchronous error on rank {rank}")
         raise
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs())
+    info.update({"batch_per_gpu": N, "global_batch": N_global, "parallelism": f"dp{world}",
+                 "allreduce": (args.allreduce if comm is not None else None),
+                 "dist_backend": (dist.get_backend() if world > 1 else None),
+                 "control_plane": (dist.get_backend() if world > 1 else None),
+                 "rccl_nranks": rccl_nranks, "launch": "eager C-ABI calls per step"})
+    out = {"metric": "Chebyshev-K fwd+bwd samples/sec", "value": round(N_global * args.steps / elapsed, 2),
+           "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+           "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
+           "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "f32",
+           "data": "synthetic (seeded inputs / labels, truncated-normal weights)",
+           "config": info}
+    if args.full:
+        out.update(full_figures_de(kernels, bound))
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu()
+    if rank == 0:
+        ctypes.CDLL(None).fflush(None)
+        os.write(json_fd, (json.dumps(out) + "\n").encode())
+    if comm is not None:
+        torch.cuda.synchronize()
+        comm.close()
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def full_figures_de(kernels, bound):
+    """--full, configs D / E: the per-kernel bursts (after the timed region) and
+    the roofline entry of the dominant kernel they give."""
     kern = kernels()
     if bound == "bytes":
         dom = max(kern, key=lambda k: kern[k]["ms"])
@@ -505,30 +599,17 @@ def run_config_de(args, rank, world, local, dev, json_fd):
                 "peak": MFMA_F32_PEAK_TF, "unit": "TFLOP/s", "frac": round(ach / MFMA_F32_PEAK_TF, 4),
                 "traffic": None, "alg_flops_per_call": k["alg_flops"], "avg_call_ms": round(k["ms"], 4),
                 "timing": "HIP events on the launch stream around back-to-back forward calls"}
-    info.update({"batch_per_gpu": N, "global_batch": N_global, "parallelism": f"dp{world}",
-                 "allreduce": (args.allreduce if comm is not None else None),
-                 "dist_backend": (dist.get_backend() if world > 1 else None),
-                 "control_plane": (dist.get_backend() if world > 1 else None),
-                 "rccl_nranks": rccl_nranks, "launch": "eager C-ABI calls per step"})
-    out = {"metric": "Chebyshev-K fwd+bwd samples/sec", "value": round(N_global * args.steps / elapsed, 2),
-           "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-           "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
-           "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "f32",
-           "data": "synthetic (seeded inputs / labels, truncated-normal weights)",
-           "config": info, "roofline": roof,
-           "kernels": {k: {kk: (round(vv, 4) if isinstance(vv, float) else vv) for kk, vv in v.items()}
-                       for k, v in kern.items()}}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu()
-    if rank == 0:
-        ctypes.CDLL(None).fflush(None)
-        os.write(json_fd, (json.dumps(out) + "\n").encode())
-    if comm is not None:
-        torch.cuda.synchronize()
-        comm.close()
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    return {"roofline": roof,
+            "kernels": {k: {kk: (round(vv, 4) if isinstance(vv, float) else vv) for kk, vv in v.items()}
+                        for k, v in kern.items()}}
+
+
+def weight_generator(dev):
+    """The generator W is drawn from: one fixed seed on every rank (rank 0's W
+    is broadcast anyway), apart from the per-rank stream of x and dy."""
+    g = torch.Generator(device=dev)
+    g.manual_seed(2017)
+    return g
 
 
 def main():
@@ -550,7 +631,14 @@ def main():
     ap.add_argument("--basis-layout", default="orders", choices=["rows", "orders"],
                     help="saved-basis layout (orders: fast kernels, Fin <= 2 only; the default: "
                          "0.8 %% more samples/s than rows over 5 alternating runs, profiles/r03_layout)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure the per-step distribution, each "
+                         "kernel alone (roofline, kernels, contraction_mfma) and the CPU baseline; "
+                         "a plain run reports the timed region only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at "
+                         "most 64 MB in all; larger arrays as a fixed seeded sample)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without its CPU leg")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--allreduce", default="rccl", choices=["rccl", "torch"],
                     help="rccl: cg_allreduce_sum_f32 on the compute stream (default); "
@@ -627,7 +715,7 @@ def main():
     g.manual_seed(2017 + rank)
     x = torch.rand((N, M, Fin), device=dev, generator=g)
     x[:, torch.as_tensor(fake, device=dev, dtype=torch.long), :] = 0
-    W = truncated_normal_(torch.empty((Fin * K, Fout), device=dev), 0.1)
+    W = truncated_normal_(torch.empty((Fin * K, Fout), device=dev), 0.1, weight_generator(dev))
     cdist.broadcast_parameters([W])
     dy = torch.randn((N, M, Fout), device=dev, generator=g)
 
@@ -686,8 +774,8 @@ def main():
                 sys.exit(f"bench.py: RCCL asynchronous error {st} on rank {rank}")
 
     # Before the warmup: ~12 ms of back-to-back forward / backward launches
-    # (the per-kernel timing bursts below, results discarded) that bring the
-    # GPU out of its idle clock state, which otherwise lasts through a short
+    # (the bursts --full times its kernels with, results discarded) that bring
+    # the GPU out of its idle clock state, which otherwise lasts through a short
     # timed region (driver's 20-step run: steps at 0.060 ms that settle at
     # 0.057 ms after ~200 steps, profiles/r03_graph).  They touch no training
     # state.  The kernel timings themselves are taken after the timed region.
@@ -727,46 +815,14 @@ def main():
     if world > 1:
         elapsed, = max_over_ranks([elapsed], dev)
 
-    # per-step distribution (SURVEY.md §8d asks for the median step): a second
-    # pass of the same steps with a HIP event between consecutive steps on
-    # the launch stream (after the contract's timed region, which stays
-    # event-free); max over ranks of each rank's median
-    nstep = max(50, min(args.steps, 400))
-    evs = [torch.cuda.Event(enable_timing=True) for _ in range(nstep + 1)]
-    if world > 1:
-        dist.barrier()
-    evs[0].record()
-    for i in range(nstep):
-        step(args.warmup + args.steps + i)
-        evs[i + 1].record()
-    torch.cuda.synchronize()
-    per_step = np.array([evs[i].elapsed_time(evs[i + 1]) for i in range(nstep)])
-    med_ms = float(np.median(per_step))
-    p90_ms = float(np.percentile(per_step, 90))
-    if world > 1:
-        med_ms, p90_ms = max_over_ranks([med_ms, p90_ms], dev)
-
-    # per-kernel timing (roofline.achieved), on the warm GPU: forward = one
-    # kernel; backward = the recurrence kernel + the tiny fixed-order dW slab reduce
-    fwd_ms = burst_ms(lambda: runner.forward(x, W, stream=stream))
-    bwd_ms = burst_ms(lambda: runner.backward(dy, W, stream=stream))
-    B = N * Fin
-    bytes_fwd, bytes_bwd, _csr = algorithmic_bytes(M, plan.nnz, B, K)
-    compulsory_fwd = 4 * (N * M * Fin + N * M * Fin * K + N * M * Fout) + 8 * plan.nnz + 4 * (M + 1)
-    fwd_kernel = "cheb_fwd_fast" if path == "resident" else "stream_fwd"
-    bwd_kernel = "cheb_bwd_fast" if path == "resident" else "stream_bwd"
-    kern = {
-        "fwd": {"kernel": fwd_kernel, "ms": fwd_ms, "alg_bytes": bytes_fwd},
-        "bwd": {"kernel": bwd_kernel + "+k_reduce_slabs", "ms": bwd_ms, "alg_bytes": bytes_bwd},
-    }
-    dom = max(kern, key=lambda k: kern[k]["ms"])
-    ach = kern[dom]["alg_bytes"] / (kern[dom]["ms"] * 1e-3) / 1e9
-    cfg_key = {"M": M, "N": N, "K": K, "Fin": Fin, "Fout": Fout, "layout": runner.basis_layout}
-    traffic, traffic_src = pmc_traffic(kern[dom]["kernel"].split("+")[0], cfg_key)
-    fwd_traffic, _ = pmc_traffic(fwd_kernel, cfg_key)
-    mfma_busy, mfma_src = pmc_mfma_busy(fwd_kernel, cfg_key)
-    contraction_tflops = 2.0 * N * M * Fin * K * Fout / (fwd_ms * 1e-3) / 1e12
-    spmm_ach = bytes_fwd / (fwd_ms * 1e-3) / 1e9
+    # what the last timed step left in the step's output buffers (the later
+    # --full passes run more steps over them); the forward schedule's current
+    # weights are the ones the last forward wrote (its last update is pending)
+    if args.dump_outputs and rank == 0:
+        j = (args.warmup + args.steps - 1) % 2 if fwd_adam else 0
+        dump_outputs(args.dump_outputs, {"y": runner.y, "dx": runner.dx, "dW": runner.dW,
+                                         "W": trainer.W[j], "adam_m": trainer.m[j],
+                                         "adam_v": trainer.v[j]})
 
     value = N_global * args.steps / elapsed
     out = {
@@ -777,9 +833,6 @@ def main():
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-        "step_ms_median": round(med_ms, 4),
-        "step_ms_p90": round(p90_ms, 4),
-        "samples_per_s_at_median": round(N_global / (med_ms * 1e-3), 1),
         "higher_is_better": True,
         "scaling": "strong" if strong else "weak",
         "vs_baseline": None,
@@ -802,33 +855,84 @@ def main():
                    "adam": ("fused into the dW reduction (cg_cheb_backward_adam)" if fuse_adam
                             else "applied by the next step's forward (cg_cheb_forward_adam)"
                             if fwd_adam else "cg_adam_update")},
-        "roofline": {"bound": "hbm", "kernel": kern[dom]["kernel"],
-                     "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(ach / HBM_PEAK_GBS, 4),
-                     "traffic": traffic,
-                     "alg_bytes_per_launch": kern[dom]["alg_bytes"],
-                     "avg_launch_ms": round(kern[dom]["ms"], 5),
-                     "timing": "HIP events on the launch stream around 50 back-to-back launches",
-                     "traffic_source": traffic_src},
-        # BASELINE.json's north-star target: >= 40 % of the HBM roofline on the
-        # K-step CSR SpMM of config B, i.e. the forward basis kernel (the
-        # headline `roofline` above is the slowest kernel of the step)
-        "roofline_spmm_fwd": {"bound": "hbm", "kernel": fwd_kernel, "achieved": round(spmm_ach, 1),
-                              "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                              "frac": round(spmm_ach / HBM_PEAK_GBS, 4), "target_frac": 0.40,
-                              "traffic": fwd_traffic, "alg_bytes_per_launch": bytes_fwd,
-                              "avg_launch_ms": round(fwd_ms, 5)},
-        "kernels": {k: {"kernel": v["kernel"], "avg_ms": round(v["ms"], 5), "alg_bytes": v["alg_bytes"],
-                        "alg_GBps": round(v["alg_bytes"] / (v["ms"] * 1e-3) / 1e9, 1)}
-                    for k, v in kern.items()},
-        "contraction_mfma": {"tflops_over_fwd_kernel": round(contraction_tflops, 2),
-                             "peak_tflops": MFMA_F32_PEAK_TF,
-                             "frac": round(contraction_tflops / MFMA_F32_PEAK_TF, 4),
-                             "busy_frac": mfma_busy, "busy_source": mfma_src},
-        "compulsory_fwd_bytes": compulsory_fwd,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(L, fake, K, Fout, seconds=args.cpu_seconds)
+
+    def full_figures():
+        """--full: the step distribution, the kernels alone and their rooflines."""
+        # per-step distribution (SURVEY.md §8d asks for the median step): a second
+        # pass of the same steps with a HIP event between consecutive steps on
+        # the launch stream (after the contract's timed region, which stays
+        # event-free); max over ranks of each rank's median
+        nstep = max(50, min(args.steps, 400))
+        evs = [torch.cuda.Event(enable_timing=True) for _ in range(nstep + 1)]
+        if world > 1:
+            dist.barrier()
+        evs[0].record()
+        for i in range(nstep):
+            step(args.warmup + args.steps + i)
+            evs[i + 1].record()
+        torch.cuda.synchronize()
+        per_step = np.array([evs[i].elapsed_time(evs[i + 1]) for i in range(nstep)])
+        med_ms = float(np.median(per_step))
+        p90_ms = float(np.percentile(per_step, 90))
+        if world > 1:
+            med_ms, p90_ms = max_over_ranks([med_ms, p90_ms], dev)
+
+        # per-kernel timing (roofline.achieved), on the warm GPU: forward = one
+        # kernel; backward = the recurrence kernel + the tiny fixed-order dW slab reduce
+        fwd_ms = burst_ms(lambda: runner.forward(x, W, stream=stream))
+        bwd_ms = burst_ms(lambda: runner.backward(dy, W, stream=stream))
+        B = N * Fin
+        bytes_fwd, bytes_bwd, _csr = algorithmic_bytes(M, plan.nnz, B, K)
+        compulsory_fwd = 4 * (N * M * Fin + N * M * Fin * K + N * M * Fout) + 8 * plan.nnz + 4 * (M + 1)
+        fwd_kernel = "cheb_fwd_fast" if path == "resident" else "stream_fwd"
+        bwd_kernel = "cheb_bwd_fast" if path == "resident" else "stream_bwd"
+        kern = {
+            "fwd": {"kernel": fwd_kernel, "ms": fwd_ms, "alg_bytes": bytes_fwd},
+            "bwd": {"kernel": bwd_kernel + "+k_reduce_slabs", "ms": bwd_ms, "alg_bytes": bytes_bwd},
+        }
+        dom = max(kern, key=lambda k: kern[k]["ms"])
+        ach = kern[dom]["alg_bytes"] / (kern[dom]["ms"] * 1e-3) / 1e9
+        cfg_key = {"M": M, "N": N, "K": K, "Fin": Fin, "Fout": Fout, "layout": runner.basis_layout}
+        traffic, traffic_src = pmc_traffic(kern[dom]["kernel"].split("+")[0], cfg_key)
+        fwd_traffic, _ = pmc_traffic(fwd_kernel, cfg_key)
+        mfma_busy, mfma_src = pmc_mfma_busy(fwd_kernel, cfg_key)
+        contraction_tflops = 2.0 * N * M * Fin * K * Fout / (fwd_ms * 1e-3) / 1e12
+        spmm_ach = bytes_fwd / (fwd_ms * 1e-3) / 1e9
+        return {
+            "step_ms_median": round(med_ms, 4),
+            "step_ms_p90": round(p90_ms, 4),
+            "samples_per_s_at_median": round(N_global / (med_ms * 1e-3), 1),
+            "roofline": {"bound": "hbm", "kernel": kern[dom]["kernel"],
+                         "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": round(ach / HBM_PEAK_GBS, 4),
+                         "traffic": traffic,
+                         "alg_bytes_per_launch": kern[dom]["alg_bytes"],
+                         "avg_launch_ms": round(kern[dom]["ms"], 5),
+                         "timing": "HIP events on the launch stream around 50 back-to-back launches",
+                         "traffic_source": traffic_src},
+            # BASELINE.json's north-star target: >= 40 % of the HBM roofline on the
+            # K-step CSR SpMM of config B, i.e. the forward basis kernel (the
+            # headline `roofline` above is the slowest kernel of the step)
+            "roofline_spmm_fwd": {"bound": "hbm", "kernel": fwd_kernel, "achieved": round(spmm_ach, 1),
+                                  "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                  "frac": round(spmm_ach / HBM_PEAK_GBS, 4), "target_frac": 0.40,
+                                  "traffic": fwd_traffic, "alg_bytes_per_launch": bytes_fwd,
+                                  "avg_launch_ms": round(fwd_ms, 5)},
+            "kernels": {k: {"kernel": v["kernel"], "avg_ms": round(v["ms"], 5), "alg_bytes": v["alg_bytes"],
+                            "alg_GBps": round(v["alg_bytes"] / (v["ms"] * 1e-3) / 1e9, 1)}
+                        for k, v in kern.items()},
+            "contraction_mfma": {"tflops_over_fwd_kernel": round(contraction_tflops, 2),
+                                 "peak_tflops": MFMA_F32_PEAK_TF,
+                                 "frac": round(contraction_tflops / MFMA_F32_PEAK_TF, 4),
+                                 "busy_frac": mfma_busy, "busy_source": mfma_src},
+            "compulsory_fwd_bytes": compulsory_fwd,
+        }
+
+    if args.full:
+        out.update(full_figures())
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline(L, fake, K, Fout, seconds=args.cpu_seconds)
     if rank == 0:
         ctypes.CDLL(None).fflush(None)  # library stdio buffers: still to stderr
         os.write(json_fd, (json.dumps(out) + "\n").encode())

@@ -15,10 +15,10 @@ timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smok
 tail -1 $OUT/smoke.txt
 timeout -k 10 1200 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread > $OUT/pytest_gpu.txt 2>&1 || { echo PYTEST_FAIL; tail -40 $OUT/pytest_gpu.txt | cut -c1-300; exit 1; }
 tail -1 $OUT/pytest_gpu.txt
-timeout -k 10 300 python bench.py --steps 200 --warmup 20 --cpu-seconds 10 > $OUT/bench.json 2>$OUT/bench.err || { echo BENCH_FAIL; tail -30 $OUT/bench.err; exit 1; }
+timeout -k 10 300 python bench.py --full --steps 200 --warmup 20 --cpu-seconds 10 > $OUT/bench.json 2>$OUT/bench.err || { echo BENCH_FAIL; tail -30 $OUT/bench.err; exit 1; }
 tail -1 $OUT/bench.json | cut -c1-300
-timeout -k 10 300 python bench.py --config E --steps 30 --warmup 3 --cpu-seconds 8 > $OUT/bench_E.json 2>$OUT/bench_E.err || { echo BENCHE_FAIL; tail -30 $OUT/bench_E.err; exit 1; }
-timeout -k 10 400 python bench.py --config D --steps 5 --warmup 1 --cpu-seconds 8 > $OUT/bench_D.json 2>$OUT/bench_D.err || { echo BENCHD_FAIL; tail -30 $OUT/bench_D.err; exit 1; }
+timeout -k 10 300 python bench.py --full --config E --steps 30 --warmup 3 --cpu-seconds 8 > $OUT/bench_E.json 2>$OUT/bench_E.err || { echo BENCHE_FAIL; tail -30 $OUT/bench_E.err; exit 1; }
+timeout -k 10 400 python bench.py --full --config D --steps 5 --warmup 1 --cpu-seconds 8 > $OUT/bench_D.json 2>$OUT/bench_D.err || { echo BENCHD_FAIL; tail -30 $OUT/bench_D.err; exit 1; }
 timeout -k 10 700 python scripts/bench_configs.py A C1 C2 D E R > $OUT/configs.jsonl 2>$OUT/configs.err || { echo CFG_FAIL; tail -20 $OUT/configs.err; exit 1; }
 grep config $OUT/configs.jsonl | cut -c1-250
 timeout -k 10 200 rocprofv3 --kernel-trace --stats -d $OUT/ktA -o A --output-format csv -- python3 scripts/bench_configs.py A --no-cpu > $OUT/ktA.log 2>&1 || { echo KTA_FAIL; tail -20 $OUT/ktA.log; exit 1; }

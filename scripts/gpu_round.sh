@@ -14,7 +14,7 @@ timeout -k 10 1000 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeou
 tail -1 $OUT/pytest_gpu.txt
 timeout -k 10 240 python scripts/ablate.py > $OUT/ablate.json 2>&1 || { echo ABLATE_FAIL; tail -20 $OUT/ablate.json; exit 1; }
 grep -v amdgpu.ids $OUT/ablate.json | head -30
-timeout -k 10 300 python bench.py --steps 200 --warmup 20 --cpu-seconds 10 > $OUT/bench.json 2>&1 || { echo BENCH_FAIL; tail -30 $OUT/bench.json; exit 1; }
+timeout -k 10 300 python bench.py --full --steps 200 --warmup 20 --cpu-seconds 10 > $OUT/bench.json 2>&1 || { echo BENCH_FAIL; tail -30 $OUT/bench.json; exit 1; }
 tail -1 $OUT/bench.json
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt --output-format csv -- python3 bench.py --steps 50 --warmup 10 --no-cpu-baseline > $OUT/kt.txt 2>&1 || { echo PROF_FAIL; tail -30 $OUT/kt.txt; exit 1; }
 find $OUT/kt -name "*kernel_stats.csv" -exec cut -c1-160 {} \; | head -12

@@ -54,6 +54,35 @@ def test_committed_pmc_summary_is_config_b():
     assert d["counters"]["cheb_bwd_fast"]["FETCH_SIZE_x2_bytes"] > 0
 
 
+def test_dump_plan_keeps_small_arrays_whole_and_stays_in_budget():
+    # config B at 256: everything fits; config D at 256: y and dx (4.3 G floats
+    # each) share what the small arrays leave of the 64 MB
+    b = {"y": 256 * 976 * 32, "dx": 256 * 976, "dW": 800, "W": 800}
+    assert bench.dump_plan(b) == b
+    d = {"y": 256 * 262144 * 64, "dx": 256 * 262144 * 64, "dW": 192 * 64, "W": 192 * 64}
+    p = bench.dump_plan(d)
+    assert p["dW"] == p["W"] == 192 * 64 and 0 < p["dx"] <= p["y"] < d["y"]
+    assert 4 * sum(p.values()) + 256 * len(p) <= bench.DUMP_BYTES == 64 * 1000 * 1000
+    assert 4 * sum(p.values()) > 0.99 * bench.DUMP_BYTES
+
+
+def test_dump_outputs_writes_float32_and_a_fixed_sample(tmp_path):
+    import numpy as np
+    import torch
+    big = torch.arange(10000, dtype=torch.float64).reshape(100, 100)
+    small = torch.arange(6, dtype=torch.float32).reshape(2, 3)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big, "small": small}, limit_bytes=4096)
+    a = {f: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(a) == ["big.npy", "small.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in a) <= 4096
+    assert a["small.npy"].dtype == np.float32 and np.array_equal(a["small.npy"], small.numpy())
+    s = a["big.npy"]   # a sorted sample of the values 0..9999, each its own index
+    assert s.dtype == np.float32 and s.ndim == 1 and 800 <= s.size < 10000
+    assert np.all(np.diff(s) >= 0) and s.min() >= 0 and s.max() <= 9999 and np.all(s == np.round(s))
+    assert np.array_equal(s, np.load(tmp_path / "b" / "big.npy"))
+
+
 def test_batch_split_weak_and_strong():
     import argparse
     weak = argparse.Namespace(batch=256, global_batch=None)

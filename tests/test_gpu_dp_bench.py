@@ -83,7 +83,7 @@ def test_bench_entry_path_world2(dev):
     512 in all; strong scaling (--global-batch 256): 128 per GPU."""
     base = ["--gpus", "2", "--allreduce", "torch", "--dist-backend", "gloo", "--steps", "20",
             "--warmup", "5"]
-    weak = _bench_json(base)
+    weak = _bench_json(base + ["--full"])
     assert weak["n_gpus"] == 2 and weak["steps"] == 20 and weak["warmup"] == 5
     assert weak["scaling"] == "weak"
     c = weak["config"]
@@ -109,7 +109,7 @@ def test_bench_config_de_entry_world2(dev, config, batch, bucket):
     per-rank batch (the full shapes otherwise).  Weak and strong scaling."""
     base = ["--config", config, "--gpus", "2", "--allreduce", "torch", "--dist-backend", "gloo",
             "--batch", str(batch), "--steps", "3", "--warmup", "1"]
-    weak = _bench_json(base)
+    weak = _bench_json(base + ["--full"])
     assert weak["n_gpus"] == 2 and weak["steps"] == 3 and weak["warmup"] == 1
     assert weak["scaling"] == "weak" and weak["metric"] == "Chebyshev-K fwd+bwd samples/sec"
     c = weak["config"]
@@ -127,13 +127,44 @@ def test_bench_config_de_entry_world2(dev, config, batch, bucket):
     assert strong["config"]["batch_per_gpu"] == batch - 1  # rank 0's shard; rank 1 takes the remainder
 
 
+FULL_ONLY = ("step_ms_median", "step_ms_p90", "roofline", "roofline_spmm_fwd", "kernels",
+             "contraction_mfma", "cpu_baseline")
+
+
+@pytest.mark.timeout(300)
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(dev, tmp_path):
+    """A plain run times its steps and nothing else: the result line carries the
+    headline fields and none of --full's.  --dump-outputs writes the last timed
+    step's arrays (float32, the runner's shapes, under 64 MB in all); the inputs
+    are seeded, so a second run with the same arguments writes the same arrays
+    (to the suite's 1e-5 normwise bar; the kernels' summation order is fixed)."""
+    args = ["--gpus", "1", "--steps", "4", "--warmup", "2"]
+    runs = []
+    for d in (tmp_path / "a", tmp_path / "b"):
+        line = _bench_json(args + ["--dump-outputs", str(d)], timeout=120)
+        assert line["steps"] == 4 and line["warmup"] == 2 and line["dtype"] == "f32"
+        assert line["unit"] == "samples/s" and line["higher_is_better"] is True
+        assert line["value"] > 0 and line["ms_per_step"] > 0
+        assert abs(line["value"] - 256 / (line["ms_per_step"] / 1e3)) < 0.01 * line["value"]
+        assert not [k for k in FULL_ONLY if k in line]
+        runs.append({f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))})
+    a, b = runs
+    assert sorted(a) == ["W", "adam_m", "adam_v", "dW", "dx", "y"]
+    assert a["y"].shape == (256, 976, 32) and a["dx"].shape == (256, 976, 1)
+    assert a["dW"].shape == a["W"].shape == a["adam_m"].shape == a["adam_v"].shape == (25, 32)
+    assert sum(v.nbytes for v in a.values()) <= 64 * 1000 * 1000
+    for k, v in a.items():
+        assert v.dtype == np.float32 and np.isfinite(v).all() and np.any(v != 0), k
+        assert O.normwise_err(b[k], v.astype(np.float64)) < 1e-5, k
+
+
 @pytest.mark.timeout(600)
 def test_bench_config_e_one_gpu_line(dev):
     """bench.py --config E at N = 1 (the 1-rank line, with its exchange forced
     through a 1-rank RCCL communicator: rccl_nranks == 1) and the contract
     fields."""
     line = _bench_json(["--config", "E", "--batch", "8", "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline", "--force-allreduce"])
+                        "--full", "--no-cpu-baseline", "--force-allreduce"])
     assert line["n_gpus"] == 1 and line["config"]["rccl_nranks"] == 1
     assert line["config"]["global_batch"] == 8 and line["config"]["parallelism"] == "dp1"
     assert line["roofline"]["unit"] == "TFLOP/s"
