@@ -104,6 +104,14 @@ _SIGNATURES = {
                            _c_int),
     "cg_fourier_backward": ([_c_i32, _c_i32, _c_i32, _c_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_sz,
                              _vp], _c_int),
+    "cg_gft_workspace_bytes": ([_c_i32, ctypes.POINTER(_c_sz)], _c_int),
+    "cg_gft_prepare": ([_c_i32, _vp, _vp, _c_sz, _vp], _c_int),
+    "cg_gft": ([_c_i32, _c_i32, _c_i32, _c_i32, _vp, _c_sz, _vp, _vp, _vp], _c_int),
+    "cg_fourier_mix": ([_c_i32, _c_i64, _c_i32, _c_i32, _c_i32, _vp, _vp, _vp, _vp, _vp, _vp], _c_int),
+    "cg_flstm_supported": ([_c_i32, _c_i32, _c_i32, ctypes.POINTER(_c_i32)], _c_int),
+    "cg_flstm_workspace_bytes": ([_c_i32, _c_i32, _c_i32, ctypes.POINTER(_c_sz)], _c_int),
+    "cg_flstm_step": ([_c_i32, _c_i32, _c_i32, _c_i32, _vp, _c_sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                       _vp, _vp, _vp, _c_sz, _vp], _c_int),
     "cg_lstm_cell_forward": ([_c_i64, _c_i32, _c_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
                              _c_int),
     "cg_lstm_cell_backward": ([_c_i64, _c_i32, _c_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],

@@ -458,6 +458,31 @@ hipError_t launch_fourier_mix_t(const float* dYh, const float* W, int N, int M, 
 hipError_t launch_fourier_dw(const float* dYh, const float* Xh, int N, int M, int Fin, int Fout,
                              float* dW, hipStream_t s);
 
+// ---- gconv-LSTM with the Fourier filter (fourier_lstm.hip) -----------------------
+// Spectral tensors are sample-major [N][M][C] like the vertex-domain ones.
+// The prepared transform operand of a graph (launch_gft_prepare): U^T and U
+// zero-padded to gft_pad(M), as bf16 split terms in MFMA fragment order and as
+// f32 k-major copies.
+int gft_pad(int M);
+size_t gft_basis_bytes(int M);
+hipError_t launch_gft_prepare(const float* U, int M, void* basis, hipStream_t s);
+// gate epilogue of a synthesis with C == 4H (the k_lstm_fwd expressions)
+struct GftGate {
+  int H, gates;
+  const float* bias;
+  const float* c_prev;  // NULL = zero state
+  float* c_out;
+  float* h_out;
+  float* act;           // [N][M][4H] gate-major, or NULL
+};
+// out[n] = U^T in[n] (inverse 0) or U in[n]; in, out [N][M][C].  g != NULL: no
+// out, the gate update instead.
+hipError_t launch_gft(const void* basis, int inverse, int N, int M, int C, const float* in,
+                      float* out, bool x3, const GftGate* g, hipStream_t s);
+// per-frequency contraction (forms of cg_fourier_mix)
+hipError_t launch_fmix(int form, int64_t R, int M, int Cin, int Cout, const float* W, const float* x,
+                       const float* g, const float* add, float* out, hipStream_t s);
+
 // ---- misc ----------------------------------------------------------------------
 hipError_t launch_perm_gather(const float* x, const int32_t* perm, int N, int M_in, int M_out,
                               int F, float* out, hipStream_t s);

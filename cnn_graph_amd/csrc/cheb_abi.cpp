@@ -1548,6 +1548,107 @@ int cg_fourier_backward(int32_t N, int32_t M, int32_t Fin, int32_t Fout, const f
   return ok();
 }
 
+// ---- gconv-LSTM with the Fourier filter (fourier_lstm.hip) -----------------------
+static int check_gft(const char* what, int32_t N, int32_t M, int32_t C, const void* basis,
+                     size_t basis_bytes) {
+  if (N < 1 || M < 1 || C < 1) return fail(CG_ERR_ARG, "%s: bad shape N=%d M=%d C=%d", what, N, M, C);
+  if (M > (1 << 20)) return fail(CG_ERR_ARG, "%s: M=%d too large", what, M);
+  if (int64_t(N) * M * C >= (int64_t(1) << 31))
+    return fail(CG_ERR_ARG, "%s: N*M*C = %lld exceeds 2^31", what, (long long)(int64_t(N) * M * C));
+  if (!basis) return fail(CG_ERR_ARG, "%s: null basis", what);
+  if (basis_bytes < cg::gft_basis_bytes(M) || (reinterpret_cast<uintptr_t>(basis) & 15))
+    return fail(CG_ERR_ARG, "%s: basis too small or not 16-byte aligned: %zu < %zu", what, basis_bytes,
+                cg::gft_basis_bytes(M));
+  return CG_OK;
+}
+
+int cg_gft_workspace_bytes(int32_t M, size_t* basis_bytes) {
+  if (M < 1 || M > (1 << 20) || !basis_bytes) return fail(CG_ERR_ARG, "gft_workspace_bytes: bad arguments");
+  *basis_bytes = cg::gft_basis_bytes(M);
+  return ok();
+}
+
+int cg_gft_prepare(int32_t M, const float* U, void* basis, size_t basis_bytes, void* stream) {
+  if (!U) return fail(CG_ERR_ARG, "gft_prepare: null U");
+  int rc = check_gft("gft_prepare", 1, M, 1, basis, basis_bytes);
+  if (rc) return rc;
+  CG_HIP(cg::launch_gft_prepare(U, M, basis, reinterpret_cast<hipStream_t>(stream)));
+  return ok();
+}
+
+int cg_gft(int32_t inverse, int32_t N, int32_t M, int32_t C, const void* basis, size_t basis_bytes,
+           const float* in, float* out, void* stream) {
+  int rc = check_gft("gft", N, M, C, basis, basis_bytes);
+  if (rc) return rc;
+  if (!in || !out || in == out) return fail(CG_ERR_ARG, "gft: null or aliased in / out");
+  CG_HIP(cg::launch_gft(basis, inverse != 0, N, M, C, in, out, cg::option(cg::kOptGemmX3) != 0,
+                        nullptr, reinterpret_cast<hipStream_t>(stream)));
+  return ok();
+}
+
+int cg_fourier_mix(int32_t form, int64_t R, int32_t M, int32_t Cin, int32_t Cout, const float* W,
+                   const float* x, const float* g, const float* add, float* out, void* stream) {
+  if (form < 0 || form > 2) return fail(CG_ERR_ARG, "fourier_mix: unknown form %d", form);
+  if (R < 1 || M < 1 || Cin < 1 || Cout < 1)
+    return fail(CG_ERR_ARG, "fourier_mix: bad shape R=%lld M=%d Cin=%d Cout=%d", (long long)R, M, Cin,
+                Cout);
+  if (R * M * int64_t(Cin > Cout ? Cin : Cout) >= (int64_t(1) << 31) ||
+      int64_t(M) * Cin * Cout >= (int64_t(1) << 31))
+    return fail(CG_ERR_ARG, "fourier_mix: a tensor exceeds 2^31 elements");
+  if (!out || (form != 2 && !W) || (form != 1 && !x) || (form != 0 && !g))
+    return fail(CG_ERR_ARG, "fourier_mix: null operand for form %d", form);
+  if (form != 0 && add) return fail(CG_ERR_ARG, "fourier_mix: add is for form 0 only");
+  CG_HIP(cg::launch_fmix(form, R, M, Cin, Cout, W, x, g, add, out,
+                         reinterpret_cast<hipStream_t>(stream)));
+  return ok();
+}
+
+static bool flstm_ok(int32_t M, int32_t H, int32_t Fin) {
+  return M >= 1 && M <= (1 << 20) && Fin >= 1 && H >= 8 && H % 8 == 0 && H <= 4096;
+}
+
+int cg_flstm_supported(int32_t M, int32_t H, int32_t Fin, int32_t* supported) {
+  if (!supported) return fail(CG_ERR_ARG, "flstm_supported: null output");
+  if (M < 1 || H < 1 || Fin < 1) return fail(CG_ERR_ARG, "flstm_supported: bad shape");
+  *supported = flstm_ok(M, H, Fin) ? 1 : 0;
+  return ok();
+}
+
+int cg_flstm_workspace_bytes(int32_t N, int32_t M, int32_t H, size_t* bytes) {
+  if (N < 1 || M < 1 || H < 1 || !bytes) return fail(CG_ERR_ARG, "flstm_workspace_bytes: bad arguments");
+  *bytes = al256(size_t(N) * M * 4 * H * 4);
+  return ok();
+}
+
+int cg_flstm_step(int32_t N, int32_t M, int32_t H, int32_t gates, const void* basis,
+                  size_t basis_bytes, const float* h_prev, const float* c_prev, const float* ghat_x,
+                  const float* Wh, const float* bias, float* c_out, float* h_out, float* act,
+                  float* hhat, void* workspace, size_t ws_bytes, void* stream) {
+  if (N < 1 || M < 1 || H < 1) return fail(CG_ERR_ARG, "flstm_step: bad shape N=%d M=%d H=%d", N, M, H);
+  if (!flstm_ok(M, H, 1)) return fail(CG_ERR_ARG, "flstm_step: needs H %% 8 == 0 (H=%d)", H);
+  if (gates != CG_LSTM_GATES_REFERENCE && gates != CG_LSTM_GATES_STANDARD)
+    return fail(CG_ERR_ARG, "flstm_step: unknown gate set %d", gates);
+  int rc = check_gft("flstm_step", N, M, 4 * H, basis, basis_bytes);
+  if (rc) return rc;
+  if (!ghat_x || !c_out || !h_out) return fail(CG_ERR_ARG, "flstm_step: null ghat_x / c_out / h_out");
+  if (h_prev && (!Wh || !hhat)) return fail(CG_ERR_ARG, "flstm_step: h_prev needs Wh and hhat");
+  const size_t need = al256(size_t(N) * M * 4 * H * 4);
+  if (h_prev && (!workspace || ws_bytes < need))
+    return fail(CG_ERR_ARG, "flstm_step workspace too small: %zu < %zu", ws_bytes, need);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const bool x3 = cg::option(cg::kOptGemmX3) != 0;
+  const float* ghat = ghat_x;
+  if (h_prev) {
+    float* sum = static_cast<float*>(workspace);
+    CG_HIP(cg::launch_gft(basis, 0, N, M, H, h_prev, hhat, x3, nullptr, s));
+    CG_HIP(cg::launch_fmix(0, N, M, H, 4 * H, Wh, hhat, nullptr, ghat_x, sum, s));
+    ghat = sum;
+  }
+  cg::GftGate g{H, gates == CG_LSTM_GATES_REFERENCE ? 0 : 1, bias, c_prev, c_out, h_out, act};
+  CG_HIP(cg::launch_gft(basis, 1, N, M, 4 * H, ghat, nullptr, x3, &g, s));
+  return ok();
+}
+
 static int check_lstm(int64_t R, int32_t H, int32_t gates) {
   if (R < 1 || H < 1) return fail(CG_ERR_ARG, "lstm: bad shape R=%lld H=%d", (long long)R, H);
   if (R * int64_t(H) * 4 >= (int64_t(1) << 31))

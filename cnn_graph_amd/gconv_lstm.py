@@ -9,6 +9,11 @@ Reference behaviour kept:
     initialiser (:173-176); ``K`` defaults to 2 (:95-96);
   * gate functions z = tan, i = f = sigmoid, o = tanh (:188, :195, :202, :209)
     -- ``gates="standard"`` gives the usual tanh / sigmoid instead;
+  * ``filter_type="fourier_conv"`` (:59, :116-133): the per-gate variables are
+    ``[nNode, feat_out, feat_in]`` spectral weights (``uniform(-0.1, 0.1)``), kept
+    concatenated along feat_out as ``Wx`` [M, 4H, Fin] and ``Wh`` [M, 4H, H];
+    ``K`` is accepted and ignored (lib/filter.py:32); ``cell.U`` is the device
+    Fourier basis;
   * ``forget_bias`` is accepted and ignored, as in the reference (:49);
   * ``__call__(inputs, state) -> (new_h, LSTMStateTuple(new_c, new_h))``.
   * ``DropoutWrapper(cell, output_keep_prob)`` (:616, :623): the cell's outputs
@@ -36,6 +41,15 @@ additionally batches the x-conv of ALL time steps into one call (it does not
 depend on the recurrence), runs the T h-steps back to back, and in the
 backward sums the h-weight gradient of all steps per Chebyshev order with one
 ``cg_weight_grad`` over the stacked steps.
+
+The Fourier cell sums the x and h contributions in the spectral domain (the
+inverse transform is linear) and synthesises once per step: a layer is one
+analysis and one per-frequency contraction for the x part of all steps, then
+three launches per step (``cg_flstm_step``: analysis of h on MFMA with the
+exact three-term bf16 split, the per-frequency accumulate on MFMA, the
+synthesis with the gate update in its epilogue).  ``hconv="unfused"`` (and any
+H that is not a multiple of 8) is the composition of ``ops.fourier_conv`` and
+the pointwise gate kernel.
 """
 from __future__ import annotations
 
@@ -82,9 +96,14 @@ class GConvLSTMCell:
                  reuse=None, laplacian=None, lmax=None, K=None, feat_in=None, nNode=None,
                  filter_type="cheby_conv", gates="reference", device=None, generator=None,
                  hconv="auto"):
+        self.filter_type = filter_type
+        if filter_type == "fourier_conv":
+            self._init_fourier(num_units, forget_bias, state_is_tuple, laplacian, lmax, K, feat_in,
+                               nNode, gates, device, generator, hconv)
+            return
         if filter_type != "cheby_conv":
-            raise NotImplementedError(f"filter_type={filter_type!r}: only the Chebyshev filter "
-                                      "is on the MI355X path (fourier_conv is out of scope)")
+            raise NotImplementedError(f"filter_type={filter_type!r}: the filters on the MI355X path "
+                                      "are 'cheby_conv' and 'fourier_conv'")
         if laplacian is None or feat_in is None:
             raise ValueError("laplacian and feat_in are required")
         if gates not in ops.LSTM_GATES:
@@ -129,6 +148,53 @@ class GConvLSTMCell:
         self.seq_x = self.seq and ops.lstm_seq_x_supported(self.plan, self._feat_in, H, self._K)
         self.fused = supported and hconv != "unfused"
 
+    def _init_fourier(self, num_units, forget_bias, state_is_tuple, laplacian, lmax, K, feat_in,
+                      nNode, gates, device, generator, hconv):
+        """filter_type="fourier_conv" (lib/gconv_lstm.py:116-133): per-gate
+        [nNode, feat_out, feat_in] variables, concatenated along feat_out in
+        the order z, i, f, o: Wx [M, 4H, Fin], Wh [M, 4H, H], b [4H]."""
+        from . import filter as _filter
+        if laplacian is None or feat_in is None:
+            raise ValueError("laplacian and feat_in are required")
+        if gates not in ops.LSTM_GATES:
+            raise ValueError(f"gates must be one of {list(ops.LSTM_GATES)}")
+        self._num_units = H = int(num_units)
+        self._forget_bias = forget_bias          # unused, as in the reference
+        self._state_is_tuple = state_is_tuple
+        self._laplacian = laplacian
+        self._lmax = 2 if lmax is None else lmax
+        self._K = 2 if K is None else int(K)      # accepted and ignored (lib/filter.py:32)
+        self._feat_in = F = int(feat_in)
+        self._nNode = M = int(nNode) if nNode is not None else int(laplacian.shape[0])
+        if M != int(laplacian.shape[0]):
+            raise ValueError(f"nNode={M} does not match the Laplacian ({laplacian.shape[0]})")
+        self.gates = gates
+        self.device = torch.device(device if device is not None else "cuda")
+        f32 = dict(device=self.device, dtype=torch.float32)
+        with torch.no_grad():
+            Wx = torch.empty((M, 4 * H, F), **f32).uniform_(-0.1, 0.1, generator=generator)
+            Wh = torch.empty((M, 4 * H, H), **f32).uniform_(-0.1, 0.1, generator=generator)
+            lim = math.sqrt(6.0 / (H + H))
+            b = torch.empty((4 * H,), **f32).uniform_(-lim, lim, generator=generator)
+        self.Wx = torch.nn.Parameter(Wx)
+        self.Wh = torch.nn.Parameter(Wh)
+        self.b = torch.nn.Parameter(b)
+        # h path: "fused" = three launches per step (analysis, per-frequency
+        # accumulate, synthesis + gates: cg_flstm_step); "unfused" = the
+        # composition of ops.fourier_conv and the pointwise gate kernel
+        if hconv == "seq":
+            raise ValueError("hconv='seq' is a Chebyshev path; the Fourier cell has 'fused' and 'unfused'")
+        if hconv not in ("auto", "fused", "unfused"):
+            raise ValueError("hconv must be 'auto', 'fused' or 'unfused'")
+        supported = ops.flstm_supported(M, H, F)
+        if hconv == "fused" and not supported:
+            raise ValueError(f"hconv='fused' needs H a multiple of 8 (H={H})")
+        self.fused = supported and hconv != "unfused"
+        self.seq = self.seq_x = False
+        self.U = _filter.fourier_basis(laplacian, self.device)  # [M, M], eigenvectors in columns
+        # U pre-split into its bf16 terms, kept with the cell
+        self.gft_basis = ops.gft_prepare(self.U) if self.fused else None
+
     # -- reference properties ---------------------------------------------------
     @property
     def state_size(self):
@@ -146,6 +212,9 @@ class GConvLSTMCell:
         v = {}
         for q, g in enumerate(GATE_NAMES):
             sl = slice(q * H, (q + 1) * H)
+            if self.filter_type == "fourier_conv":  # [nNode, feat_out, feat_in] per gate
+                v[f"W{g}xt"], v[f"W{g}ht"], v[f"b{g}t"] = self.Wx[:, sl, :], self.Wh[:, sl, :], self.b[sl]
+                continue
             v[f"W{g}xt"] = self.Wx[:, sl]
             v[f"W{g}ht"] = self.Wh[:, sl]
             v[f"b{g}t"] = self.b[sl]
@@ -166,7 +235,10 @@ class GConvLSTMCell:
             c, h = state
         else:
             c, h = torch.split(state, self._nNode, dim=1)  # tf.split(state, 2, axis=1) (:82)
-        new_c, new_h = _CellStep.apply(inputs, c, h, self.Wx, self.Wh, self.b, self)
+        if self.filter_type == "fourier_conv":
+            new_c, new_h = _fourier_cell_step(self, inputs, c, h)
+        else:
+            new_c, new_h = _CellStep.apply(inputs, c, h, self.Wx, self.Wh, self.b, self)
         if self._state_is_tuple:
             new_state = LSTMStateTuple(new_c, new_h)
         else:
@@ -418,6 +490,143 @@ class _Layer(torch.autograd.Function):
         return dx_out, dc0, dh0, dWx, dWh, db, None, None, None, None
 
 
+class _FourierGates(torch.autograd.Function):
+    """The pointwise gate update on pre-activation parts gx, gh [N, M, 4H]
+    (ops.lstm_cell_forward / backward) for the unfused Fourier composition."""
+
+    @staticmethod
+    def forward(ctx, gx, gh, b, c, H, gates):
+        c = c.contiguous()
+        c_out, h_out, act = ops.lstm_cell_forward(gx.contiguous(), gh.contiguous(), b, c, H, gates)
+        ctx.save_for_backward(act, c, c_out)
+        ctx.H, ctx.gates = H, gates
+        return c_out, h_out
+
+    @staticmethod
+    def backward(ctx, dc_out, dh_out):
+        act, c, c_out = ctx.saved_tensors
+        dh = dh_out.contiguous() if dh_out is not None else None
+        dc = dc_out.contiguous() if dc_out is not None else None
+        dpre, dc_prev = ops.lstm_cell_backward(dh, None, dc, act, c, c_out, ctx.H, ctx.gates)
+        return dpre, dpre, ops.bias_grad(dpre), dc_prev, None, None
+
+
+def _fourier_unfused_step(cell, x, c, h):
+    """(c', h') as the composition of the existing ops: two spectral filters
+    with the concatenated weights and the pointwise gate kernel."""
+    gx = ops.fourier_conv(x, cell.Wx, cell.U)
+    gh = ops.fourier_conv(h, cell.Wh, cell.U)
+    return _FourierGates.apply(gx, gh, cell.b, c, cell._num_units, cell.gates)
+
+
+def _fourier_cell_step(cell, x, c, h):
+    if not cell.fused:
+        return _fourier_unfused_step(cell, x, c, h)
+    _, new_c, new_h = _FourierLayer.apply(x.unsqueeze(0), c.contiguous(), h.contiguous(), cell.Wx,
+                                          cell.Wh, cell.b, cell, False, True)
+    return new_c, new_h
+
+
+class _FourierLayer(torch.autograd.Function):
+    """static_rnn of one Fourier cell over a [T, N, M, F] sequence (a single
+    cell step is T = 1).  Forward: ONE analysis of all T*N inputs, ONE
+    per-frequency contraction giving the x part of every step's spectral
+    pre-activations, then per step the three-launch h-step (cg_flstm_step; step
+    0 of a zero-state layer is the synthesis + gates alone).  Backward: per
+    step the gate backward, the analysis of dpre, the transposed contraction
+    with Wh and a synthesis give the gradient of h_{t-1}; after the loop dWh
+    and dWx are ONE weight-gradient launch each over the stacked steps."""
+
+    @staticmethod
+    def forward(ctx, xs, c0, h0, Wx, Wh, b, cell: GConvLSTMCell, zero_init: bool,
+                want_c: bool = True):
+        H, gates, basis = cell._num_units, cell.gates, cell.gft_basis
+        xs = xs.contiguous()
+        T, N, M, F = xs.shape
+        f32 = dict(device=xs.device, dtype=torch.float32)
+        xhat = ops.gft(basis, xs.view(T * N, M, F))
+        ghx = ops.fourier_mix("fwd", Wx, x=xhat).view(T, N, M, 4 * H)
+        hs = torch.empty((T, N, M, H), **f32)
+        cs = torch.empty((T, N, M, H), **f32)
+        act = torch.empty((T, N, M, 4 * H), **f32)
+        hhat = torch.empty((T, N, M, H), **f32)  # U^T h_{t-1}: the weight gradient's operand
+        for t in range(T):
+            h_prev = (None if zero_init else h0) if t == 0 else hs[t - 1]
+            c_prev = (None if zero_init else c0) if t == 0 else cs[t - 1]
+            ops.flstm_step(basis, h_prev, c_prev, ghx[t], Wh, b, gates, out_c=cs[t], out_h=hs[t],
+                           out_act=act[t], out_hhat=hhat[t])
+        ctx.save_for_backward(xhat, hhat, Wx, Wh, act, cs, c0)
+        ctx.cell, ctx.zero_init, ctx.shape = cell, zero_init, (T, N, M, F)
+        ctx.set_materialize_grads(False)
+        cT = cs[T - 1].clone() if want_c else cs.new_empty(0)
+        return hs, cT, hs[T - 1].clone()
+
+    @staticmethod
+    def backward(ctx, dhs, dcT, dhT):
+        xhat, hhat, Wx, Wh, act, cs, c0 = ctx.saved_tensors
+        cell, zero_init = ctx.cell, ctx.zero_init
+        H, gates, basis = cell._num_units, cell.gates, cell.gft_basis
+        T, N, M, F = ctx.shape
+        f32 = dict(device=act.device, dtype=torch.float32)
+        dpre = torch.empty((T, N, M, 4 * H), **f32)
+        dghat = torch.empty((T, N, M, 4 * H), **f32)
+        dhs = dhs.contiguous() if dhs is not None else None
+        dc = dcT.contiguous() if dcT is not None else None
+        dh_last = None  # the gradient of h_{T-1}: through hs and through h_T
+        if dhT is not None:
+            dh_last = dhT.contiguous() if dhs is None else dhs[T - 1] + dhT
+        elif dhs is not None:
+            dh_last = dhs[T - 1]
+        dh_rec = None
+        t_first = 1 if zero_init else 0  # first step whose h part ran
+        dhhat = torch.empty((N, M, H), **f32)
+        for t in range(T - 1, -1, -1):
+            c_prev = (None if zero_init else c0) if t == 0 else cs[t - 1]
+            dh_t = dh_last if t == T - 1 else (None if dhs is None else dhs[t])
+            _, dc = ops.lstm_cell_backward(dh_t, dh_rec, dc, act[t], c_prev, cs[t], H, gates,
+                                           out_dpre=dpre[t])
+            ops.gft(basis, dpre[t], out=dghat[t])  # a = U ghat  ->  d ghat = U^T dpre
+            if t >= t_first:
+                ops.fourier_mix("t", Wh, g=dghat[t], out=dhhat)
+                dh_rec = ops.gft(basis, dhhat, inverse=True)
+            else:
+                dh_rec = None
+        if T > t_first:  # the stacked (t, n) rows of every step with an h part, one launch
+            dWh = ops.fourier_mix("dw", x=hhat[t_first:], g=dghat[t_first:])
+        else:
+            dWh = torch.zeros_like(Wh)
+        dWx = ops.fourier_mix("dw", x=xhat, g=dghat)
+        db = ops.bias_grad(dpre)
+        dxs = None
+        if ctx.needs_input_grad[0]:
+            dxhat = ops.fourier_mix("t", Wx, g=dghat.view(T * N, M, 4 * H))
+            dxs = ops.gft(basis, dxhat, inverse=True).view(T, N, M, F)
+        return (dxs, None if zero_init else dc, None if zero_init else dh_rec, dWx, dWh, db,
+                None, None, None)
+
+
+def _fourier_layer(cell, xs, initial_state, final_c):
+    """layer() for a Fourier cell."""
+    if not cell.fused:  # the composition, step by step under autograd
+        if initial_state is None:
+            c, h = cell.zero_state(xs.shape[1])
+        else:
+            c, h = initial_state
+        outs = []
+        for t in range(xs.shape[0]):
+            c, h = _fourier_unfused_step(cell, xs[t], c, h)
+            outs.append(h)
+        return torch.stack(outs), LSTMStateTuple(c if final_c else c.new_empty(0), h)
+    if initial_state is None:
+        z = xs.new_empty(0)
+        hs, cT, hT = _FourierLayer.apply(xs, z, z, cell.Wx, cell.Wh, cell.b, cell, True, final_c)
+    else:
+        c0, h0 = initial_state
+        hs, cT, hT = _FourierLayer.apply(xs, c0.contiguous(), h0.contiguous(), cell.Wx, cell.Wh,
+                                         cell.b, cell, False, final_c)
+    return hs, LSTMStateTuple(cT, hT)
+
+
 class DropoutWrapper:
     """tf.nn.rnn_cell.DropoutWrapper(cell, output_keep_prob) as glstm_layer
     wraps every layer's cell (lib/gconv_lstm.py:616, :623): the cell's OUTPUTS
@@ -471,6 +680,8 @@ def layer(cell, xs: torch.Tensor, initial_state=None, final_c: bool = True):
     if isinstance(cell, DropoutWrapper):
         hs, state = layer(cell.cell, xs, initial_state, final_c)
         return ops.dropout(hs, cell.output_keep_prob, cell.next_seed()), state
+    if cell.filter_type == "fourier_conv":
+        return _fourier_layer(cell, xs, initial_state, final_c)
     ins = [xs, cell.Wx, cell.Wh, cell.b] + ([] if initial_state is None else list(initial_state))
     check_now = not (torch.is_grad_enabled() and any(t.requires_grad for t in ins))
     if initial_state is None:
@@ -540,7 +751,9 @@ class GLSTMModel:
       x [N, M, F*T]  --unstack time (:272-275)-->  T x [N, M, F]
       glstm_layer    layer_count GConvLSTMCells under static_rnn (:609-627),
                      each in a DropoutWrapper(output_keep_prob) (:616, :623)
-      fc_layer       out = cheby_conv(outputs[-1]; W_fc [K*H, Fout]) (:629-636)
+      fc_layer       out = cheby_conv(outputs[-1]; W_fc [K*H, Fout]) (:629-636); with
+                     filter="fourier_conv" the cells and the fc layer use the
+                     Fourier filter (Wx [M, 4H, Fin], Wh [M, 4H, H], W_fc [M, Fout, H])
       loss           mean((labels - out)^2) + its moving average    cg_mse_loss_ema
       exchange       ONE all-reduce(sum) of the flat gradient bucket (N > 1)
       update         ONE optimizer launch over the flat parameter buffer,
@@ -562,9 +775,12 @@ class GLSTMModel:
                  layer_count: int = 1, out_features: int = 2, keep_prob: float = 0.8,
                  optimizer: str = "adam", learning_rate: float = 1e-3, decay_rate: float = 0.95,
                  decay_steps: int | None = None, lmax: float = 2, gates: str = "reference",
-                 device=None, seed: int = 2017, comm=None):
+                 device=None, seed: int = 2017, comm=None, filter: str = "cheby_conv"):
         if optimizer not in self.OPTIMIZERS:
             raise ValueError(f"optimizer must be one of {self.OPTIMIZERS}")
+        if filter not in ("cheby_conv", "fourier_conv"):
+            raise ValueError("filter must be 'cheby_conv' or 'fourier_conv'")
+        self.filter = filter
         self.device = torch.device(device if device is not None else "cuda")
         self.N, self.T, self.F, self.H, self.K = int(N), int(T), int(feat_in), int(num_hidden), int(K)
         self.Fout = int(out_features)
@@ -577,11 +793,16 @@ class GLSTMModel:
         for li in range(int(layer_count)):
             fin = self.F if li == 0 else self.H
             cells.append(GConvLSTMCell(self.H, laplacian=L, lmax=lmax, K=self.K, feat_in=fin,
-                                       gates=gates, device=self.device, generator=gen))
-        self.plan = cells[0].plan
-        self.M = self.plan.M
+                                       gates=gates, device=self.device, generator=gen,
+                                       filter_type=filter))
+        fourier = filter == "fourier_conv"
+        self.plan = None if fourier else cells[0].plan
+        self.U = cells[0].U if fourier else None
+        self.M = cells[0]._nNode
         H, K = self.H, self.K
-        sizes = [c.Wx.numel() + c.Wh.numel() + c.b.numel() for c in cells] + [K * H * self.Fout]
+        # fc_layer (lib/gconv_lstm.py:629-636) uses the same filter by name
+        fc_shape = (self.M, self.Fout, H) if fourier else (K * H, self.Fout)
+        sizes = [c.Wx.numel() + c.Wh.numel() + c.b.numel() for c in cells] + [math.prod(fc_shape)]
         f32 = dict(device=self.device, dtype=torch.float32)
         total = sum(sizes)
         self.flat = torch.empty(total, **f32)
@@ -608,7 +829,7 @@ class GLSTMModel:
                 c.Wh = bind(c.Wh.detach(), scope.format(li) + "Wh")
                 c.b = bind(c.b.detach(), scope.format(li) + "b")
         with torch.no_grad():
-            w0 = truncated_normal_(torch.empty((K * H, self.Fout), **f32), 0.1, gen)
+            w0 = truncated_normal_(torch.empty(fc_shape, **f32), 0.1, gen)
             self.W_fc = bind(w0, "conv_init/weights")
         assert off == total
         self.cells = cells
@@ -676,6 +897,8 @@ class GLSTMModel:
             if drop:
                 h = ops.dropout(h, cell.output_keep_prob, cell.next_seed(),
                                 offset=(xs.shape[0] - 1) * h.numel())
+        if self.filter == "fourier_conv":
+            return ops.fourier_conv(h, self.W_fc, self.U)
         return ops.cheb_conv(h, self.W_fc, self.plan, self.K)
 
     def train_step(self, x, labels, stream=None):

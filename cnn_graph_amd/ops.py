@@ -1045,6 +1045,125 @@ def fourier_conv(x, W, U):
     return _Fourier.apply(x, W, U)
 
 
+# -- gconv-LSTM with the Fourier filter (lib/gconv_lstm.py:116-133, :183-221) --------
+# Spectral tensors keep the sample-major layout of the vertex-domain ones,
+# [..., M, C] with the frequency in the place of the vertex.
+def gft_prepare(U: torch.Tensor) -> torch.Tensor:
+    """The graph's transform operand for gft / flstm_step, prepared once from
+    U [M, M] (cg_gft_prepare): an opaque uint8 device buffer."""
+    _check_dev("U", U)
+    U = U.contiguous()
+    M = int(U.shape[0])
+    if tuple(U.shape) != (M, M):
+        raise ValueError(f"U must be square, got {tuple(U.shape)}")
+    nb = ctypes.c_size_t()
+    _lib.call("cg_gft_workspace_bytes", M, ctypes.byref(nb))
+    basis = torch.empty(nb.value, device=U.device, dtype=torch.uint8)
+    _lib.call("cg_gft_prepare", M, _p(U), _p(basis), nb.value, _stream(U))
+    return basis
+
+
+def gft(basis: torch.Tensor, x: torch.Tensor, inverse: bool = False, out: torch.Tensor | None = None):
+    """Batched graph Fourier transform of x [..., M, C]: U^T x per sample
+    (analysis) or U x (inverse=True, synthesis), on MFMA (cg_gft)."""
+    _check_dev("x", x)
+    x = x.contiguous()
+    M, C = int(x.shape[-2]), int(x.shape[-1])
+    N = x.numel() // (M * C)
+    if out is None:
+        out = torch.empty(tuple(x.shape), device=x.device, dtype=torch.float32)
+    _check_out("out", out, (N, M, C))
+    _lib.call("cg_gft", int(bool(inverse)), N, M, C, _p(basis), basis.numel(), _p(x), _p(out),
+              _stream(x))
+    return out
+
+
+FOURIER_MIX_FORMS = {"fwd": 0, "t": 1, "dw": 2}
+
+
+def fourier_mix(form: str, W=None, x=None, g=None, add=None, out=None):
+    """Per-frequency contraction on MFMA (cg_fourier_mix); W [M, Cout, Cin],
+    x [..., M, Cin], g [..., M, Cout]:
+      "fwd": add + W[m] x[., m, :]  -> [..., M, Cout]   (add None = 0; out may be add)
+      "t":   W[m]^T g[., m, :]      -> [..., M, Cin]
+      "dw":  sum over rows of g (x) x -> [M, Cout, Cin] (fixed order: bitwise reproducible)"""
+    f = FOURIER_MIX_FORMS[form]
+    ref = x if f != 1 else g
+    for name, t in (("W", W), ("x", x), ("g", g), ("add", add)):
+        if t is not None:
+            _check_dev(name, t)
+            if not t.is_contiguous():
+                raise ValueError(f"{name}: must be contiguous")
+    if f != 2:
+        M, Cout, Cin = (int(s) for s in W.shape)
+    else:
+        M, Cin, Cout = int(x.shape[-2]), int(x.shape[-1]), int(g.shape[-1])
+    R = ref.numel() // (M * int(ref.shape[-1]))
+    lead = tuple(ref.shape[:-2])
+    if x is not None and (f != 1) and (int(x.shape[-2]), int(x.shape[-1])) != (M, Cin):
+        raise ValueError(f"x: need [..., {M}, {Cin}], got {tuple(x.shape)}")
+    if g is not None and (f != 0) and ((int(g.shape[-2]), int(g.shape[-1])) != (M, Cout) or
+                                       g.numel() != R * M * Cout):
+        raise ValueError(f"g: need {R} rows of [{M}, {Cout}], got {tuple(g.shape)}")
+    shape = (lead + (M, Cout), lead + (M, Cin), (M, Cout, Cin))[f]
+    if out is None:
+        out = torch.empty(shape, device=ref.device, dtype=torch.float32)
+    n = 1
+    for s in shape:
+        n *= s
+    _check_out("out", out, (n,))
+    if add is not None and add.numel() != n:
+        raise ValueError(f"add: bad shape {tuple(add.shape)}")
+    _lib.call("cg_fourier_mix", f, R, M, Cin, Cout, _p(W), _p(x) if f != 1 else None,
+              _p(g) if f != 0 else None, _p(add), _p(out), _stream(ref))
+    return out
+
+
+def flstm_supported(M: int, H: int, Fin: int) -> bool:
+    """Whether cg_flstm_step serves this hidden size (H a multiple of 8)."""
+    ok = ctypes.c_int32()
+    _lib.call("cg_flstm_supported", int(M), int(H), int(Fin), ctypes.byref(ok))
+    return bool(ok.value)
+
+
+def flstm_step(basis, h_prev, c_prev, ghat_x, Wh, bias, gates="reference", out_c=None, out_h=None,
+               out_act=None, out_hhat=None):
+    """One forward step of the Fourier gconv-LSTM's recurrent part
+    (cg_flstm_step: analysis of h_prev, per-frequency accumulate onto ghat_x,
+    synthesis with the gate update in its epilogue).  ghat_x [N, M, 4H]; h_prev,
+    c_prev [N, M, H] or None (zero state).  Returns (c', h', act, hhat)."""
+    _check_dev("ghat_x", ghat_x)
+    N, M, H4 = (int(s) for s in ghat_x.shape)
+    H = H4 // 4
+    R = N * M
+    dev = ghat_x.device
+    for name, t, n in (("h_prev", h_prev, R * H), ("c_prev", c_prev, R * H), ("bias", bias, 4 * H),
+                       ("Wh", Wh, M * 4 * H * H), ("ghat_x", ghat_x, R * 4 * H)):
+        if t is not None:
+            _check_dev(name, t)
+            if not t.is_contiguous() or t.numel() != n:
+                raise ValueError(f"{name}: bad shape {tuple(t.shape)}")
+    f32 = dict(device=dev, dtype=torch.float32)
+    c_out = out_c if out_c is not None else torch.empty((N, M, H), **f32)
+    h_out = out_h if out_h is not None else torch.empty((N, M, H), **f32)
+    act = out_act if out_act is not None else torch.empty((N, M, 4 * H), **f32)
+    _check_out("c_out", c_out, (R, H))
+    _check_out("h_out", h_out, (R, H))
+    _check_out("act", act, (R, 4 * H))
+    hhat, ws, nbytes = None, None, 0
+    if h_prev is not None:
+        hhat = out_hhat if out_hhat is not None else torch.empty((N, M, H), **f32)
+        _check_out("hhat", hhat, (R, H))
+        nb = ctypes.c_size_t()
+        _lib.call("cg_flstm_workspace_bytes", N, M, H, ctypes.byref(nb))
+        nbytes = nb.value
+        ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    _lib.call("cg_flstm_step", N, M, H, LSTM_GATES[gates], _p(basis), basis.numel(), _p(h_prev),
+              _p(c_prev), _p(ghat_x), _p(Wh), _p(bias), _p(c_out), _p(h_out), _p(act), _p(hhat),
+              _p(ws), nbytes, _stream(ghat_x))
+    return c_out, h_out, act, hhat
+
+
 # -- stacked-input ResGNN pieces (lib/graph_conv.py:272-303) -----------------------
 class _SliceChannels(torch.autograd.Function):
     @staticmethod

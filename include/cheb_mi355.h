@@ -347,6 +347,58 @@ int cg_fourier_backward(int32_t N, int32_t M, int32_t Fin, int32_t Fout, const f
                         void* workspace, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * gconv-LSTM with the Fourier filter (lib/gconv_lstm.py:116-133, :183-221 with
+ * filter_type = "fourier_conv"; lib/filter.py:11-42).  Additive to version 301.
+ *
+ * Spectral tensors use the SAME sample-major layout as the vertex-domain
+ * tensors, [N][M][C] with frequency m in the place of the vertex: the steps of
+ * a layer are contiguous slices of one [T][N][M][C] buffer.
+ *
+ * basis: the graph's transform operand, prepared ONCE per graph from U
+ * (cg_gft_prepare; cg_gft_workspace_bytes of device memory, 16-byte aligned):
+ * U^T and U zero-padded, each as the three bf16 terms of the exact split in
+ * MFMA fragment order, plus f32 copies for CG_OPT_GEMM_X3 = 0.
+ *
+ * cg_gft: out[n] = U^T in[n] (inverse == 0, analysis) or U in[n] (inverse != 0,
+ * synthesis) for in, out [N][M][C], any C >= 1, any M >= 1; no transpose
+ * passes.  CG_OPT_GEMM_X3 = 1 (default): f32-accurate on the bf16 matrix pipe;
+ * 0: f32 MFMA.  in and out must not alias.
+ *
+ * cg_fourier_mix: the per-frequency contraction on MFMA, W [M][Cout][Cin],
+ * x [R][M][Cin], g [R][M][Cout] (R = rows: samples, or the stacked (t, n) of
+ * a layer):
+ *   form 0  out[r][m][:] = add[r][m][:] + W[m] x[r][m][:]    out [R][M][Cout]
+ *           (add may be NULL, or out itself = accumulate)
+ *   form 1  out[r][m][:] = W[m]^T g[r][m][:]                   out [R][M][Cin]
+ *   form 2  out[m] = sum_r g[r][m][:] (x) x[r][m][:]           out [M][Cout][Cin]
+ *           (r in increasing order: two runs agree bitwise)
+ * Unused operands of a form are ignored (may be NULL).
+ *
+ * cg_flstm_step: one forward step of the cell's recurrent part in three
+ * launches -- hhat = U^T h_prev (kept: the weight gradient needs it),
+ * ghat = ghat_x + Wh hhat per frequency, then a = U ghat + bias with the gate
+ * update in the synthesis' epilogue (the pre-activations never reach memory).
+ * ghat_x [N][M][4H] is the x part (form 0 of U^T x).  h_prev NULL = zero h
+ * state: the synthesis + gates alone (hhat and the workspace are not used).
+ * c_prev NULL = zero c state.  Writes c_out, h_out [N][M][H] and act
+ * [N][M][4H] gate-major (what cg_lstm_cell_forward writes; may be NULL).
+ * workspace: cg_flstm_workspace_bytes.  gates as cg_lstm_cell_forward.
+ * Needs H % 8 == 0 (cg_flstm_supported).
+ * ------------------------------------------------------------------------- */
+int cg_gft_workspace_bytes(int32_t M, size_t* basis_bytes);
+int cg_gft_prepare(int32_t M, const float* U, void* basis, size_t basis_bytes, void* stream);
+int cg_gft(int32_t inverse, int32_t N, int32_t M, int32_t C, const void* basis, size_t basis_bytes,
+           const float* in, float* out, void* stream);
+int cg_fourier_mix(int32_t form, int64_t R, int32_t M, int32_t Cin, int32_t Cout, const float* W,
+                   const float* x, const float* g, const float* add, float* out, void* stream);
+int cg_flstm_supported(int32_t M, int32_t H, int32_t Fin, int32_t* supported);
+int cg_flstm_workspace_bytes(int32_t N, int32_t M, int32_t H, size_t* bytes);
+int cg_flstm_step(int32_t N, int32_t M, int32_t H, int32_t gates, const void* basis,
+                  size_t basis_bytes, const float* h_prev, const float* c_prev, const float* ghat_x,
+                  const float* Wh, const float* bias, float* c_out, float* h_out, float* act,
+                  float* hhat, void* workspace, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
  * gconv-LSTM cell pointwise part (lib/gconv_lstm.py:77-221, GConvLSTMCell).
  * The cell's eight cheby_conv calls are two chebyshev5 calls with the four
  * gate weights concatenated: gx = cheb(x; [Wzxt|Wixt|Wfxt|Woxt]) and

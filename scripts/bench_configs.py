@@ -6,6 +6,8 @@
   C2  same graph, layer 2:                  N=128, Fin=32, K=5, Fout=32
   D   Chung-Lu 2^18 vertices, nnz 4.19M:    N=--d-batch (default 32), Fin=Fout=64, K=3
   E   gconv-LSTM layer on grid(32) 8-NN:    T=12, N=128, Fin=2, H=32, K=3 (fwd+bwd, BPTT)
+  EF  the same layer with the Fourier filter (filter_type="fourier_conv"): hconv="fused"
+      against hconv="unfused", the h-step's launches and the transforms' share of peak
 
 fwd / bwd are HIP-event timings (torch's current stream, where every C-ABI
 call is enqueued) of one chebyshev5 forward and backward (dx + dW), median of
@@ -131,6 +133,91 @@ def lstm_config(dev, T=12, N=128, Fin=2, H=32, K=3, hconv="auto"):
             "samples_per_s": round(N / (fb * 1e-3), 1)}
 
 
+F32_MATRIX_PEAK = 155e12  # measured v_mfma_f32_32x32x2_f32 rate; the x3 roof is 2.7x it
+
+
+def flstm_config(dev, T=12, N=128, Fin=2, H=32, samples=8):
+    """EF: one gconv-LSTM layer with the Fourier filter on config E's grid graph,
+    forward + backward.  hconv="fused" against hconv="unfused" (the composition
+    of ops.fourier_conv and the pointwise gate kernel: code that predates the
+    fused path, the baseline), alternating, one event pair per pass; plus the
+    three launches of the h-step and the transforms' share of the matrix peaks."""
+    from cnn_graph_amd.gconv_lstm import GConvLSTMCell, layer
+    _, L = graph_e()
+    M = L.shape[0]
+    g = torch.Generator(device=dev)
+    g.manual_seed(2)
+    cells = {h: GConvLSTMCell(H, laplacian=L, lmax=2, feat_in=Fin, device=dev, hconv=h,
+                              filter_type="fourier_conv") for h in ("fused", "unfused")}
+    xs = torch.rand((T, N, M, Fin), device=dev, generator=g)
+    gh = torch.randn((T, N, M, H), device=dev, generator=g)
+
+    def fwdbwd(cell):
+        hs, _ = layer(cell, xs)
+        hs.backward(gh)
+        for p in cell.parameters():
+            p.grad = None
+
+    def one(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    for c in cells.values():  # warm every shape of the timed window
+        fwdbwd(c)
+        fwdbwd(c)
+    torch.cuda.synchronize()
+    ms = {h: [] for h in cells}
+    for _ in range(samples):  # alternate the two legs
+        for h, c in cells.items():
+            ms[h].append(one(lambda: fwdbwd(c)))
+    stat = {h: [float(np.percentile(v, q)) for q in (50, 10, 90)] for h, v in ms.items()}
+    # the h-step's launches and the backward's wide analysis, alone
+    cell = cells["fused"]
+    B = cell.gft_basis
+    f32 = dict(device=dev, dtype=torch.float32)
+    h_prev, c_prev = torch.randn((N, M, H), generator=g, **f32), torch.randn((N, M, H), generator=g, **f32)
+    ghx = torch.randn((N, M, 4 * H), generator=g, **f32) * 0.1
+    hhat, gsum = ops.gft(B, h_prev), torch.empty((N, M, 4 * H), **f32)
+    co, ho, act = (torch.empty(s, **f32) for s in ((N, M, H), (N, M, H), (N, M, 4 * H)))
+    launches = {
+        "analysis_H": lambda: ops.gft(B, h_prev, out=hhat),
+        "mix_accumulate": lambda: ops.fourier_mix("fwd", cell.Wh, x=hhat, add=ghx, out=gsum),
+        "synthesis_gates": lambda: ops.flstm_step(B, None, c_prev, gsum, None, cell.b, out_c=co,
+                                                  out_h=ho, out_act=act),
+        "analysis_4H": lambda: ops.gft(B, ghx, out=gsum),
+    }
+    lt = {}
+    for name, fn in launches.items():
+        fn()
+        torch.cuda.synchronize()
+        lt[name] = ev_ms(fn, 10)
+    flop = {"analysis_H": 2.0 * M * M * N * H, "synthesis_gates": 2.0 * M * M * N * 4 * H,
+            "analysis_4H": 2.0 * M * M * N * 4 * H}
+    tflops = {k: flop[k] / (lt[k] * 1e-3) / 1e12 for k in flop}
+    # transform FLOP of a layer's forward + backward (xs needs no gradient)
+    layer_flop = 2.0 * M * M * N * (T * Fin + (T - 1) * H + T * 4 * H + T * 4 * H + (T - 1) * H)
+    f, u = stat["fused"], stat["unfused"]
+    from cnn_graph_amd import _lib
+    return {"config": "EF", "M": M, "T": T, "N": N, "Fin": Fin, "H": H, "samples": samples,
+            "gemm_x3": _lib.get_option("gemm_x3"),
+            "fused_ms": round(f[0], 3), "fused_p10_p90": [round(f[1], 3), round(f[2], 3)],
+            "unfused_ms": round(u[0], 3), "unfused_p10_p90": [round(u[1], 3), round(u[2], 3)],
+            "ratio_unfused_over_fused": round(u[0] / f[0], 3),
+            "fused_wins_by_more_than_baseline_spread": bool(u[0] - f[0] > u[2] - u[1]),
+            "launch_ms": {k: round(v, 4) for k, v in lt.items()},
+            "transform_TFLOPs": {k: round(v, 1) for k, v in tflops.items()},
+            "transform_frac_f32_matrix_peak": {k: round(v * 1e12 / F32_MATRIX_PEAK, 3)
+                                               for k, v in tflops.items()},
+            "transform_frac_x3_roof": {k: round(v * 1e12 / (2.7 * F32_MATRIX_PEAK), 3)
+                                       for k, v in tflops.items()},
+            "layer_transform_GFLOP": round(layer_flop / 1e9, 1),
+            "layer_transform_TFLOPs_end_to_end": round(layer_flop / (f[0] * 1e-3) / 1e12, 1)}
+
+
 def resgnn_config(dev, N=100, Fin=2, nfilter=32, K=20, nres=4):
     """ResGNN training step (§8f-1, lib/graph_model.py:246-310 with
     lib/graph_conv.py:305-330): the humanflow-ln-period shape (M = 1024,
@@ -211,6 +298,8 @@ def main():
             out = lstm_config(dev)
             cpu = lambda: bench.cpu_baseline_lstm(graph_e()[0], 8, 128, 12, 2, 32, 3,  # noqa: E731
                                                   seconds=args.cpu_seconds)
+        elif name == "EF":
+            out = flstm_config(dev)
         elif name == "E_unfused":
             out = lstm_config(dev, hconv="unfused")
         elif name == "E_step":
