@@ -50,16 +50,33 @@ exact three-term bf16 split, the per-frequency accumulate on MFMA, the
 synthesis with the gate update in its epilogue).  ``hconv="unfused"`` (and any
 H that is not a multiple of 8) is the composition of ``ops.fourier_conv`` and
 the pointwise gate kernel.
+
+Which code runs.  ``hconv="auto"`` resolves to the first row that applies; a
+single ``cell(x, state)`` step is ``_StepLayer`` at T = 1 (``_FourierLayer``
+for the fused Fourier cell) and never takes the sequence kernel.  Launches
+per time step of a layer; the x-conv of all steps, the weight gradients and
+the bias gradient are per layer:
+
+  cell              layer() runs     forward, per step        backward, per step
+  ----------------  ---------------  -----------------------  -------------------------
+  .seq and .seq_x   _SeqLayer        1 / T (x-conv included)  1 (cg_lstm_bwd_step)
+  .seq              _SeqLayer        1 / T                    1 (cg_lstm_bwd_step)
+  .fused            _StepLayer       1 (cg_lstm_hconv_step)   pointwise + chebyshev5 dx
+  neither           _StepLayer       chebyshev5 + pointwise   pointwise + chebyshev5 dx
+  Fourier .fused    _FourierLayer    3 (cg_flstm_step)        pointwise + 3
+  Fourier unfused   autograd of ops  2 fourier_conv + gates   their backwards
+
+(``.seq``: H = 32, M <= 1024, K <= 4, L~ in LDS; ``.seq_x``: also feat_in <= 8;
+``.fused``: H = 32, M <= 1024; Fourier ``.fused``: H a multiple of 8.)
 """
 from __future__ import annotations
 
 import collections
+import ctypes
+import itertools
 import math
 
 import torch
-
-import ctypes
-import itertools
 
 from . import _lib
 from . import ops
@@ -90,18 +107,18 @@ GATE_NAMES = ("z", "i", "f", "o")
 class GConvLSTMCell:
     """lib/gconv_lstm.py:29-221 on the HIP kernels.  Parameters live in
     ``Wx`` [K*feat_in, 4H], ``Wh`` [K*H, 4H], ``b`` [4H]; ``variables`` maps the
-    reference's variable names (``Wzxt``, ``Wiht``, ``bft``, ...) to views."""
+    reference's variable names (``Wzxt``, ``Wiht``, ``bft``, ...) to views.
+    With filter_type="fourier_conv" (lib/gconv_lstm.py:116-133) the per-gate
+    [nNode, feat_out, feat_in] variables are concatenated along feat_out in
+    the order z, i, f, o: ``Wx`` [M, 4H, Fin], ``Wh`` [M, 4H, H]."""
 
     def __init__(self, num_units, forget_bias=1.0, state_is_tuple=True, activation=None,
                  reuse=None, laplacian=None, lmax=None, K=None, feat_in=None, nNode=None,
                  filter_type="cheby_conv", gates="reference", device=None, generator=None,
                  hconv="auto"):
         self.filter_type = filter_type
-        if filter_type == "fourier_conv":
-            self._init_fourier(num_units, forget_bias, state_is_tuple, laplacian, lmax, K, feat_in,
-                               nNode, gates, device, generator, hconv)
-            return
-        if filter_type != "cheby_conv":
+        fourier = filter_type == "fourier_conv"
+        if not fourier and filter_type != "cheby_conv":
             raise NotImplementedError(f"filter_type={filter_type!r}: the filters on the MI355X path "
                                       "are 'cheby_conv' and 'fourier_conv'")
         if laplacian is None or feat_in is None:
@@ -113,85 +130,69 @@ class GConvLSTMCell:
         self._state_is_tuple = state_is_tuple
         self._laplacian = laplacian
         self._lmax = 2 if lmax is None else lmax  # graph.lmax(normalized L) == 2
-        self._K = 2 if K is None else int(K)      # :95-96
-        self._feat_in = int(feat_in)
-        self._nNode = int(nNode) if nNode is not None else int(laplacian.shape[0])
+        # :95-96; the Fourier filter accepts and ignores it (lib/filter.py:32)
+        self._K = K = 2 if K is None else int(K)
+        self._feat_in = F = int(feat_in)
+        self._nNode = M = int(nNode) if nNode is not None else int(laplacian.shape[0])
+        if fourier and M != int(laplacian.shape[0]):
+            raise ValueError(f"nNode={M} does not match the Laplacian ({laplacian.shape[0]})")
         self.gates = gates
         self.device = torch.device(device if device is not None else "cuda")
-        dev_index = self.device.index if self.device.index is not None else 0
-        self.plan = plan_for(laplacian, lmax=self._lmax, device=dev_index)
-        K, F = self._K, self._feat_in
+        if not fourier:
+            dev_index = self.device.index if self.device.index is not None else 0
+            self.plan = plan_for(laplacian, lmax=self._lmax, device=dev_index)
+        wx_shape, wh_shape = ((M, 4 * H, F), (M, 4 * H, H)) if fourier else \
+            ((K * F, 4 * H), (K * H, 4 * H))
         f32 = dict(device=self.device, dtype=torch.float32)
         with torch.no_grad():
-            Wx = torch.empty((K * F, 4 * H), **f32).uniform_(-0.1, 0.1, generator=generator)
-            Wh = torch.empty((K * H, 4 * H), **f32).uniform_(-0.1, 0.1, generator=generator)
+            Wx = torch.empty(wx_shape, **f32).uniform_(-0.1, 0.1, generator=generator)
+            Wh = torch.empty(wh_shape, **f32).uniform_(-0.1, 0.1, generator=generator)
             lim = math.sqrt(6.0 / (H + H))  # glorot_uniform of a [H] vector: fan_in = fan_out = H
             b = torch.empty((4 * H,), **f32).uniform_(-lim, lim, generator=generator)
         self.Wx = torch.nn.Parameter(Wx)
         self.Wh = torch.nn.Parameter(Wh)
         self.b = torch.nn.Parameter(b)
-        # h path: "seq" = the whole layer's T steps in one launch
-        # (cg_lstm_seq_forward) and one launch per BPTT step (cg_lstm_bwd_step);
-        # "fused" = one launch per forward step (cg_lstm_hconv_step); "unfused"
-        # = chebyshev5 + pointwise kernel; "auto" picks the first that applies
+        if fourier:
+            self._resolve_fourier_hconv(hconv)
+        else:
+            self._resolve_cheby_hconv(hconv)
+
+    def _resolve_cheby_hconv(self, hconv):
+        """h path: "seq" = the whole layer's T steps in one launch
+        (cg_lstm_seq_forward) and one launch per BPTT step (cg_lstm_bwd_step);
+        "fused" = one launch per forward step (cg_lstm_hconv_step); "unfused"
+        = chebyshev5 + pointwise kernel; "auto" picks the first that applies."""
+        H, K = self._num_units, self._K
         if hconv not in ("auto", "seq", "fused", "unfused"):
             raise ValueError("hconv must be 'auto', 'seq', 'fused' or 'unfused'")
-        supported = ops.lstm_hconv_supported(self.plan, H, self._K)
-        seq_ok = ops.lstm_seq_supported(self.plan, H, self._K)
+        supported = ops.lstm_hconv_supported(self.plan, H, K)
+        seq_ok = ops.lstm_seq_supported(self.plan, H, K)
         if hconv == "fused" and not supported:
             raise ValueError(f"hconv='fused' needs H = 32 and M <= 1024 (H={H}, M={self.plan.M})")
         if hconv == "seq" and not seq_ok:
             raise ValueError(f"hconv='seq' needs H = 32, M <= 1024, K <= 4 and L~ in LDS "
-                             f"(H={H}, M={self.plan.M}, K={self._K})")
+                             f"(H={H}, M={self.plan.M}, K={K})")
         self.seq = seq_ok and hconv in ("auto", "seq")
         # feat_in <= 8: the x-conv runs inside the sequence kernel too
-        self.seq_x = self.seq and ops.lstm_seq_x_supported(self.plan, self._feat_in, H, self._K)
+        self.seq_x = self.seq and ops.lstm_seq_x_supported(self.plan, self._feat_in, H, K)
         self.fused = supported and hconv != "unfused"
 
-    def _init_fourier(self, num_units, forget_bias, state_is_tuple, laplacian, lmax, K, feat_in,
-                      nNode, gates, device, generator, hconv):
-        """filter_type="fourier_conv" (lib/gconv_lstm.py:116-133): per-gate
-        [nNode, feat_out, feat_in] variables, concatenated along feat_out in
-        the order z, i, f, o: Wx [M, 4H, Fin], Wh [M, 4H, H], b [4H]."""
+    def _resolve_fourier_hconv(self, hconv):
+        """h path: "fused" = three launches per step (analysis, per-frequency
+        accumulate, synthesis + gates: cg_flstm_step); "unfused" = the
+        composition of ops.fourier_conv and the pointwise gate kernel."""
         from . import filter as _filter
-        if laplacian is None or feat_in is None:
-            raise ValueError("laplacian and feat_in are required")
-        if gates not in ops.LSTM_GATES:
-            raise ValueError(f"gates must be one of {list(ops.LSTM_GATES)}")
-        self._num_units = H = int(num_units)
-        self._forget_bias = forget_bias          # unused, as in the reference
-        self._state_is_tuple = state_is_tuple
-        self._laplacian = laplacian
-        self._lmax = 2 if lmax is None else lmax
-        self._K = 2 if K is None else int(K)      # accepted and ignored (lib/filter.py:32)
-        self._feat_in = F = int(feat_in)
-        self._nNode = M = int(nNode) if nNode is not None else int(laplacian.shape[0])
-        if M != int(laplacian.shape[0]):
-            raise ValueError(f"nNode={M} does not match the Laplacian ({laplacian.shape[0]})")
-        self.gates = gates
-        self.device = torch.device(device if device is not None else "cuda")
-        f32 = dict(device=self.device, dtype=torch.float32)
-        with torch.no_grad():
-            Wx = torch.empty((M, 4 * H, F), **f32).uniform_(-0.1, 0.1, generator=generator)
-            Wh = torch.empty((M, 4 * H, H), **f32).uniform_(-0.1, 0.1, generator=generator)
-            lim = math.sqrt(6.0 / (H + H))
-            b = torch.empty((4 * H,), **f32).uniform_(-lim, lim, generator=generator)
-        self.Wx = torch.nn.Parameter(Wx)
-        self.Wh = torch.nn.Parameter(Wh)
-        self.b = torch.nn.Parameter(b)
-        # h path: "fused" = three launches per step (analysis, per-frequency
-        # accumulate, synthesis + gates: cg_flstm_step); "unfused" = the
-        # composition of ops.fourier_conv and the pointwise gate kernel
+        H = self._num_units
         if hconv == "seq":
             raise ValueError("hconv='seq' is a Chebyshev path; the Fourier cell has 'fused' and 'unfused'")
         if hconv not in ("auto", "fused", "unfused"):
             raise ValueError("hconv must be 'auto', 'fused' or 'unfused'")
-        supported = ops.flstm_supported(M, H, F)
+        supported = ops.flstm_supported(self._nNode, H, self._feat_in)
         if hconv == "fused" and not supported:
             raise ValueError(f"hconv='fused' needs H a multiple of 8 (H={H})")
         self.fused = supported and hconv != "unfused"
         self.seq = self.seq_x = False
-        self.U = _filter.fourier_basis(laplacian, self.device)  # [M, M], eigenvectors in columns
+        self.U = _filter.fourier_basis(self._laplacian, self.device)  # [M, M], eigenvectors in columns
         # U pre-split into its bf16 terms, kept with the cell
         self.gft_basis = ops.gft_prepare(self.U) if self.fused else None
 
@@ -211,13 +212,8 @@ class GConvLSTMCell:
         H = self._num_units
         v = {}
         for q, g in enumerate(GATE_NAMES):
-            sl = slice(q * H, (q + 1) * H)
-            if self.filter_type == "fourier_conv":  # [nNode, feat_out, feat_in] per gate
-                v[f"W{g}xt"], v[f"W{g}ht"], v[f"b{g}t"] = self.Wx[:, sl, :], self.Wh[:, sl, :], self.b[sl]
-                continue
-            v[f"W{g}xt"] = self.Wx[:, sl]
-            v[f"W{g}ht"] = self.Wh[:, sl]
-            v[f"b{g}t"] = self.b[sl]
+            sl = slice(q * H, (q + 1) * H)  # the gate's feat_out slice: axis 1 for both filters
+            v[f"W{g}xt"], v[f"W{g}ht"], v[f"b{g}t"] = self.Wx[:, sl], self.Wh[:, sl], self.b[sl]
         return v
 
     def parameters(self):
@@ -235,61 +231,20 @@ class GConvLSTMCell:
             c, h = state
         else:
             c, h = torch.split(state, self._nNode, dim=1)  # tf.split(state, 2, axis=1) (:82)
-        if self.filter_type == "fourier_conv":
-            new_c, new_h = _fourier_cell_step(self, inputs, c, h)
+        # a single step is a layer of T = 1 with a given state; a .seq cell steps
+        # too (the sequence kernel is layer()'s)
+        if self.filter_type == "fourier_conv" and not self.fused:
+            new_c, new_h = _fourier_unfused_step(self, inputs, c, h)
         else:
-            new_c, new_h = _CellStep.apply(inputs, c, h, self.Wx, self.Wh, self.b, self)
+            args = (inputs.unsqueeze(0), c.contiguous(), h.contiguous(), self.Wx, self.Wh, self.b,
+                    self, False, True)
+            _, new_c, new_h = _FourierLayer.apply(*args) if self.filter_type == "fourier_conv" \
+                else _StepLayer.apply(*args, True)
         if self._state_is_tuple:
             new_state = LSTMStateTuple(new_c, new_h)
         else:
             new_state = torch.cat([new_c, new_h], 1)  # tf.concat([new_c, new_h], 1) (:220)
         return new_h, new_state
-
-
-class _CellStep(torch.autograd.Function):
-    """One cell step: x-conv, h-conv (4 gates each, one basis per input),
-    fused gates; backward = gates backward, two chebyshev5 backwards, bias sum."""
-
-    @staticmethod
-    def forward(ctx, x, c, h, Wx, Wh, b, cell: GConvLSTMCell):
-        H, K = cell._num_units, cell._K
-        plan = cell.plan
-        x, c, h = x.contiguous(), c.contiguous(), h.contiguous()
-        basis_x, gx = ops.cheb_forward(plan, x, Wx, K)
-        if cell.fused:
-            N, M, _ = h.shape
-            planes = torch.empty((max(K - 1, 1), N * M, H), device=h.device, dtype=torch.float32)
-            c_out, h_out, act = ops.lstm_hconv_step(plan, h, c, gx, Wh, b, K, cell.gates,
-                                                    planes=planes[0], plane_stride=N * M * H)
-            ctx.save_for_backward(basis_x, planes, h, Wx, Wh, act, c, c_out)
-        else:
-            basis_h, gh = ops.cheb_forward(plan, h, Wh, K)
-            c_out, h_out, act = ops.lstm_cell_forward(gx, gh, b, c, H, cell.gates)
-            ctx.save_for_backward(basis_x, basis_h, h, Wx, Wh, act, c, c_out)
-        ctx.cell = cell
-        return c_out, h_out
-
-    @staticmethod
-    def backward(ctx, dc_out, dh_out):
-        basis_x, hb, h, Wx, Wh, act, c, c_out = ctx.saved_tensors
-        cell = ctx.cell
-        H, K, plan = cell._num_units, cell._K, cell.plan
-        dh = dh_out.contiguous() if dh_out is not None else None
-        dc = dc_out.contiguous() if dc_out is not None else None
-        if cell.fused and cell.seq:  # one launch: gates backward + the h-conv's dh
-            dpre, dc_prev, dh_prev = ops.lstm_bwd_step(plan, dh, None, dc, act, c, c_out, Wh, K,
-                                                       cell.gates)
-        else:
-            dpre, dc_prev = ops.lstm_cell_backward(dh, None, dc, act, c, c_out, H, cell.gates)
-        dx, dWx = ops.cheb_backward(plan, dpre, basis_x, Wx, K, need_dx=ctx.needs_input_grad[0])
-        if cell.fused:
-            if not cell.seq:
-                dh_prev, _ = ops.cheb_backward(plan, dpre, None, Wh, K, need_dW=False)
-            dWh = _hweight_grad_planes([h.view(-1, H)], [hb[k] for k in range(K - 1)], [dpre], H, K)
-        else:
-            dh_prev, dWh = ops.cheb_backward(plan, dpre, hb, Wh, K)
-        db = ops.bias_grad(dpre)
-        return dx, dc_prev, dh_prev, dWx, dWh, db, None
 
 
 def _hweight_grad_planes(t0_parts, planes, dpre_parts, H: int, K: int):
@@ -315,159 +270,209 @@ def _hweight_grad_planes(t0_parts, planes, dpre_parts, H: int, K: int):
     return tmp.permute(1, 0, 2).reshape(K * H, 4 * H)
 
 
-class _Layer(torch.autograd.Function):
-    """static_rnn of one cell over a [T, N, M, F] sequence (time-batched x-conv,
-    T h-convs, BPTT with one weight-gradient GEMM for the h-weights)."""
+def _prev_state(t: int, zero_init: bool, s0, ss):
+    """The state entering step t: ss[t-1], the given s0 at t = 0, None = zero."""
+    if t > 0:
+        return ss[t - 1]
+    return None if zero_init else s0
+
+
+def _bptt_grads(dhs, dcT, dhT, T: int):
+    """What every layer backward starts from: (dc, dh_at) -- dc the contiguous
+    gradient of c_T (or None) and dh_at(t) the gradient reaching h_t from
+    outside the recurrence (or None).  h_{T-1} is reached twice: through hs
+    and through h_T."""
+    dhs = dhs.contiguous() if dhs is not None else None
+    dc = dcT.contiguous() if dcT is not None else None
+    dh_last = None
+    if dhT is not None:
+        dh_last = dhT.contiguous() if dhs is None else dhs[T - 1] + dhT
+    elif dhs is not None:
+        dh_last = dhs[T - 1]
+
+    def dh_at(t):
+        return dh_last if t == T - 1 else (None if dhs is None else dhs[t])
+
+    return dc, dh_at
+
+
+def _final_c(ctx, cs, want_c: bool):
+    """c_T as an output of its own, or -- the caller does not read it -- an
+    empty placeholder that autograd refuses to differentiate (no 16 MB copy)."""
+    if want_c:
+        return cs[-1].clone()
+    z = cs.new_empty(0)
+    ctx.mark_non_differentiable(z)
+    return z
+
+
+class _SeqLayer(torch.autograd.Function):
+    """static_rnn of one ``cell.seq`` cell over a [T, N, M, F] sequence: all T
+    steps in ONE launch (with ``cell.seq_x`` the x-conv too, else the x-conv of
+    every step batched in front), BPTT with one launch per step, then the
+    weight gradients over all steps at once."""
 
     @staticmethod
-    def forward(ctx, xs, c0, h0, Wx, Wh, b, cell: GConvLSTMCell, zero_init: bool,
-                check_now: bool, want_c: bool = True):
+    def forward(ctx, xs, c0, h0, Wx, Wh, b, cell: GConvLSTMCell, zero_init: bool, want_c: bool,
+                check_now: bool):
         H, K, plan, gates = cell._num_units, cell._K, cell.plan, cell.gates
         xs = xs.contiguous()
         T, N, M, F = xs.shape
         R = N * M
-        dev = xs.device
-        f32 = dict(device=dev, dtype=torch.float32)
-        seq_x = cell.seq and cell.seq_x
-        if seq_x:  # the x-conv inside the sequence kernel; its basis kept as planes
-            basis_x, gx = torch.empty((K, T * R, F), device=dev, dtype=torch.float32), None
+        f32 = dict(device=xs.device, dtype=torch.float32)
+        if cell.seq_x:  # the x-conv inside the sequence kernel; its basis kept as planes
+            basis_x = torch.empty((K, T * R, F), **f32)
         else:  # x-conv of every step at once: a batch of T*N samples
             basis_x, gx = ops.cheb_forward(plan, xs.view(T * N, M, F), Wx, K)
-            gx = gx.view(T, R, 4 * H)
-        hs = torch.empty((T, N, M, H), **f32)
+        # a hand-off fault of an earlier launch on this plan not reported yet
+        ops.lstm_seq_fault(plan, wait=False)
         cs = torch.empty((T, N, M, H), **f32)
-        act = torch.empty((T, R, 4 * H), **f32)  # unit-major [R][H][4] on the seq path
-        fused = cell.fused or cell.seq
-        # h bases kept for the backward's weight gradient: the fused h-step
-        # writes the orders 1..K-1 as planes [K-1][T][R][H] (order 0 is h_prev)
-        planes = torch.empty((max(K - 1, 1), T, R, H), **f32) if fused and not cell.seq else None
-        basis_h = None if fused else torch.empty((T, R, H * K), **f32)
-        gh = None if fused else torch.empty((N, M, 4 * H), **f32)
-        if cell.seq:
-            # a hand-off fault of an earlier launch on this plan not reported yet
-            ops.lstm_seq_fault(plan, wait=False)
-            # all T steps in one launch.  The h basis of every step as K planes
-            # [K][T+1][R][H] of one buffer: plane 0 at t = h_{t-1} (hs IS
-            # plane 0 shifted by one step, slot 0 = h0), planes k >= 1 written
-            # by the kernel -- so the h-weight gradient is ONE planes-layout
-            # GEMM over all orders and steps
-            hp = torch.empty((K, T + 1, R, H), **f32)
-            if not zero_init:
-                hp[0, 0].copy_(h0.reshape(R, H))
-            elif seq_x:  # no h-conv at step 0: zero rows for the one-pass weight gradients
+        act = torch.empty((T, R, 4 * H), **f32)  # unit-major [R][H][4]
+        # The h basis of every step as K planes [K][T+1][R][H] of one buffer:
+        # plane 0 at t = h_{t-1} (hs IS plane 0 shifted by one step, slot 0 =
+        # h0), planes k >= 1 written by the kernel -- so the h-weight gradient
+        # is ONE planes-layout GEMM over all orders and steps
+        hp = torch.empty((K, T + 1, R, H), **f32)
+        hs = hp[0, 1:].view(T, N, M, H)
+        state = dict(h0=None if zero_init else h0, c0=None if zero_init else c0, out_hs=hs,
+                     out_cs=cs, out_act=act, planes=hp[1] if K > 1 else None,
+                     plane_stride=(T + 1) * R * H)
+        if not zero_init:
+            hp[0, 0].copy_(h0.reshape(R, H))
+        if cell.seq_x:
+            if zero_init:  # no h-conv at step 0: zero rows for the one-pass weight gradients
                 hp[:, 0].zero_()
-            hs = hp[0, 1:].view(T, N, M, H)
-            planes = hp
-            if seq_x:
-                ops.lstm_seq_forward_x(plan, xs, Wx, Wh, b, K, gates, h0=None if zero_init else h0,
-                                       c0=None if zero_init else c0, out_hs=hs, out_cs=cs,
-                                       out_act=act, planes=hp[1] if K > 1 else None,
-                                       plane_stride=(T + 1) * R * H, xplanes=basis_x)
-            else:
-                ops.lstm_seq_forward(plan, gx, Wh, b, K, T, N, gates, h0=None if zero_init else h0,
-                                     c0=None if zero_init else c0, out_hs=hs, out_cs=cs,
-                                     out_act=act, planes=hp[1] if K > 1 else None,
-                                     plane_stride=(T + 1) * R * H)
-            # a lost pair hand-off leaves NaN in hs / cs / act: an inference call
-            # checks the launch before returning its outputs, a training call
-            # before its backward consumes them (one event wait, no device sync)
-            if check_now:
-                ops.lstm_seq_fault(plan, wait=True)
-        for t in range(0 if cell.seq else T):
-            h_prev = (None if zero_init else h0) if t == 0 else hs[t - 1]
-            c_prev = (None if zero_init else c0) if t == 0 else cs[t - 1]
-            if h_prev is not None and fused:  # one launch: h-conv + gates
-                ops.lstm_hconv_step(plan, h_prev, c_prev, gx[t], Wh, b, K, gates, out_c=cs[t],
-                                    out_h=hs[t], out_act=act[t], planes=planes[0, t],
-                                    plane_stride=T * R * H)
-                continue
-            if h_prev is not None:
-                ops.cheb_forward(plan, h_prev, Wh, K, out_basis=basis_h[t], out_y=gh)
-            ops.lstm_cell_forward(gx[t], gh if h_prev is not None else None, b, c_prev, H, gates,
-                                  out_c=cs[t], out_h=hs[t], out_act=act[t])
-        ctx.save_for_backward(basis_x, planes if fused else basis_h, Wx, Wh, act, cs, c0, h0, hs)
-        ctx.cell, ctx.zero_init, ctx.shape, ctx.fused = cell, zero_init, (T, N, M, F), fused
-        ctx.seq_x = seq_x
+            ops.lstm_seq_forward_x(plan, xs, Wx, Wh, b, K, gates, xplanes=basis_x, **state)
+        else:
+            ops.lstm_seq_forward(plan, gx.view(T, R, 4 * H), Wh, b, K, T, N, gates, **state)
+        # a lost pair hand-off leaves NaN in hs / cs / act: an inference call
+        # checks the launch before returning its outputs, a training call
+        # before its backward consumes them (one event wait, no device sync)
+        if check_now:
+            ops.lstm_seq_fault(plan, wait=True)
+        ctx.save_for_backward(basis_x, hp, Wx, Wh, act, cs, c0)
+        ctx.cell, ctx.zero_init, ctx.shape = cell, zero_init, (T, N, M, F)
         # outputs nobody differentiates reach the backward as None (no zero
         # [T, N, M, H] gradient materialised for a sequence read only at its
         # last step: h_T is an output of its own)
         ctx.set_materialize_grads(False)
-        cT = cs[T - 1].clone() if want_c else cs.new_empty(0)  # (a 16 MB copy nobody reads)
-        return hs, cT, hs[T - 1].clone()
+        return hs, _final_c(ctx, cs, want_c), hs[T - 1].clone()
+
+    @staticmethod
+    def backward(ctx, dhs, dcT, dhT):
+        basis_x, hp, Wx, Wh, act, cs, c0 = ctx.saved_tensors
+        cell, zero_init = ctx.cell, ctx.zero_init
+        H, K, plan, gates = cell._num_units, cell._K, cell.plan, cell.gates
+        # a fault already known raises now; the blocking check runs after the
+        # backward is queued (a wait here would idle the GPU while the host
+        # queues the backward), before any gradient is returned
+        ops.lstm_seq_fault(plan, wait=False)
+        T, N, M, F = ctx.shape
+        R = N * M
+        dpre = torch.empty((T, R, 4 * H), device=act.device, dtype=torch.float32)
+        dc, dh_at = _bptt_grads(dhs, dcT, dhT, T)
+        dh_rec = None
+        t_first = 1 if zero_init else 0  # first step whose h-conv ran
+        for t in range(T - 1, -1, -1):
+            # one launch: gates backward, dBasis = dpre Wh^T on MFMA and the
+            # reverse recurrence over L~^T -> the gradient of h_{t-1} (None at a
+            # step that ran no h-conv: the pointwise part alone)
+            _, dc, dh_rec = ops.lstm_bwd_step(plan, dh_at(t), dh_rec, dc, act[t],
+                                              _prev_state(t, zero_init, c0, cs), cs[t], Wh, K, gates,
+                                              out_dpre=dpre[t], act_unit_major=True,
+                                              need_dh_prev=t >= t_first)
+        dy = dpre.view(T * N, M, 4 * H)
+        need_dx = ctx.needs_input_grad[0]
+        if cell.seq_x:
+            # dWh, dWx and db in ONE pass over dpre: the h planes of every step
+            # (a zero-state layer's step 0 has none: the forward zeroed its slots) and
+            # the x planes [K][T*R][F] (dx needs no basis)
+            dWh, dWx, db = ops.lstm_weight_grads(hp[0, 0:T].reshape(-1, H), (T + 1) * R * H,
+                                                 basis_x[0], T * R * F, K, T * R, dpre)
+            dxs = ops.cheb_backward(plan, dy, None, Wx, K, need_dW=False)[0] if need_dx else None
+        else:
+            if T <= t_first:
+                dWh = torch.zeros_like(Wh)
+            else:  # one GEMM over the K planes of every step with an h-conv
+                dWh = ops.weight_grad_planes(hp[0, t_first:T].reshape(-1, H), (T + 1) * R * H, K,
+                                             (T - t_first) * R, dpre[t_first:])
+            dxs, dWx = ops.cheb_backward(plan, dy, basis_x, Wx, K, need_dx=need_dx)
+            db = ops.bias_grad(dpre)
+        # raises CGError if the forward's launch lost a pair hand-off
+        ops.lstm_seq_fault(plan, wait=True)
+        return (dxs.view(T, N, M, F) if dxs is not None else None, None if zero_init else dc,
+                None if zero_init else dh_rec, dWx, dWh, db, None, None, None, None)
+
+
+class _StepLayer(torch.autograd.Function):
+    """static_rnn of one cell over a [T, N, M, F] sequence, one h-step per time
+    step (a single cell step is T = 1 with a given state): the x-conv of every
+    step batched in front, T h-steps, BPTT per step, then the h-weight
+    gradient of all steps summed per Chebyshev order."""
+
+    @staticmethod
+    def forward(ctx, xs, c0, h0, Wx, Wh, b, cell: GConvLSTMCell, zero_init: bool, want_c: bool,
+                step: bool):
+        H, K, plan, gates = cell._num_units, cell._K, cell.plan, cell.gates
+        xs = xs.contiguous()
+        T, N, M, F = xs.shape
+        R = N * M
+        f32 = dict(device=xs.device, dtype=torch.float32)
+        # x-conv of every step at once: a batch of T*N samples
+        basis_x, gx = ops.cheb_forward(plan, xs.view(T * N, M, F), Wx, K)
+        gx = gx.view(T, R, 4 * H)
+        hs = torch.empty((T, N, M, H), **f32)
+        cs = torch.empty((T, N, M, H), **f32)
+        act = torch.empty((T, R, 4 * H), **f32)
+        # h bases kept for the backward's weight gradient: the fused h-step
+        # writes the orders 1..K-1 as planes [K-1][T][R][H] (order 0 is h_prev),
+        # chebyshev5 the rows [T][R][H*K]
+        if cell.fused:
+            hb = torch.empty((max(K - 1, 1), T, R, H), **f32)
+        else:
+            hb = torch.empty((T, R, H * K), **f32)
+            gh = torch.empty((N, M, 4 * H), **f32)
+        for t in range(T):
+            h_prev = _prev_state(t, zero_init, h0, hs)
+            c_prev = _prev_state(t, zero_init, c0, cs)
+            if h_prev is None:  # step 0 of a zero-state layer: no h-conv
+                ops.lstm_cell_forward(gx[t], None, b, c_prev, H, gates, out_c=cs[t], out_h=hs[t],
+                                      out_act=act[t])
+            elif cell.fused:  # one launch: h-conv + gates
+                ops.lstm_hconv_step(plan, h_prev, c_prev, gx[t], Wh, b, K, gates, out_c=cs[t],
+                                    out_h=hs[t], out_act=act[t], planes=hb[0, t],
+                                    plane_stride=T * R * H)
+            else:
+                ops.cheb_forward(plan, h_prev, Wh, K, out_basis=hb[t], out_y=gh)
+                ops.lstm_cell_forward(gx[t], gh, b, c_prev, H, gates, out_c=cs[t], out_h=hs[t],
+                                      out_act=act[t])
+        ctx.save_for_backward(basis_x, hb, Wx, Wh, act, cs, c0, h0, hs)
+        ctx.cell, ctx.zero_init, ctx.shape = cell, zero_init, (T, N, M, F)
+        ctx.set_materialize_grads(False)  # (as in _SeqLayer)
+        if step:  # the caller reads (c, h) of its one step, not hs: no copies
+            return None, cs[0], hs[0]
+        return hs, _final_c(ctx, cs, want_c), hs[T - 1].clone()
 
     @staticmethod
     def backward(ctx, dhs, dcT, dhT):
         basis_x, hb, Wx, Wh, act, cs, c0, h0, hs = ctx.saved_tensors
-        cell, zero_init, fused = ctx.cell, ctx.zero_init, ctx.fused
-        H, K, plan, gates = cell._num_units, cell._K, cell.plan, cell.gates
-        if cell.seq:  # a fault already known raises now; the blocking check runs
-            # after the backward is queued (a wait here would idle the GPU while
-            # the host queues the backward), before any gradient is returned
-            ops.lstm_seq_fault(plan, wait=False)
+        cell, zero_init = ctx.cell, ctx.zero_init
+        H, K, plan = cell._num_units, cell._K, cell.plan
         T, N, M, F = ctx.shape
         R = N * M
-        dev = act.device
-        dpre = torch.empty((T, R, 4 * H), device=dev, dtype=torch.float32)
-        dhs = dhs.contiguous() if dhs is not None else None
-        dc = dcT.contiguous() if dcT is not None else None
-        dh_last = None  # the gradient of h_{T-1}: through hs and through h_T
-        if dhT is not None:
-            dh_last = dhT.contiguous() if dhs is None else dhs[T - 1] + dhT
-        elif dhs is not None:
-            dh_last = dhs[T - 1]
-
-        def dh_at(t):
-            return dh_last if t == T - 1 else (None if dhs is None else dhs[t])
-
+        dpre = torch.empty((T, R, 4 * H), device=act.device, dtype=torch.float32)
+        dc, dh_at = _bptt_grads(dhs, dcT, dhT, T)
         dh_rec = None
         t_first = 1 if zero_init else 0  # first step whose h-conv ran
+        # a lone unfused step: its h-conv's backward gives dWh along with dh
+        lone = T == 1 and t_first == 0 and not cell.fused
         for t in range(T - 1, -1, -1):
-            c_prev = (None if zero_init else c0) if t == 0 else cs[t - 1]
-            if cell.seq and t < t_first:  # no h-conv at this step: pointwise only, act as stored
-                _, dc, _ = ops.lstm_bwd_step(plan, dh_at(t), dh_rec, dc,
-                                             act[t], c_prev, cs[t], Wh, K, gates, out_dpre=dpre[t],
-                                             act_unit_major=True, need_dh_prev=False)
-                dh_rec = None
-                continue
-            if cell.seq and t >= t_first:
-                # one launch: gates backward, dBasis = dpre Wh^T on MFMA and the
-                # reverse recurrence over L~^T -> the gradient of h_{t-1}
-                _, dc, dh_rec = ops.lstm_bwd_step(plan, dh_at(t), dh_rec,
-                                                  dc, act[t], c_prev, cs[t], Wh, K, gates,
-                                                  out_dpre=dpre[t], act_unit_major=True)
-                continue
-            # the sequence kernel's act records are unit-major: gate-major for the
-            # pointwise kernel (step 0 of a zero-state layer only)
-            act_t = act[t].view(R, H, 4).transpose(1, 2).reshape(R, 4 * H) if cell.seq else act[t]
-            dpre_t, dc = ops.lstm_cell_backward(dh_at(t), dh_rec, dc, act_t,
-                                                c_prev, cs[t], H, gates, out_dpre=dpre[t])
-            if t >= t_first:
-                dh_rec, _ = ops.cheb_backward(plan, dpre[t].view(N, M, 4 * H),
-                                              None if fused else hb[t].view(R, H * K), Wh, K,
-                                              need_dW=False)
-            else:
-                dh_rec = None
-        if ctx.seq_x:
-            # dWh, dWx and db in ONE pass over dpre: the h planes of every step
-            # (a zero-state layer's step 0 has none: the forward zeroed its slots) and
-            # the x planes [K][T*R][F] (dx needs no basis)
-            dWh, dWx, db = ops.lstm_weight_grads(hb[0, 0:T].reshape(-1, H), (T + 1) * R * H,
-                                                 basis_x[0], T * R * F, K, T * R, dpre)
-            dxs = None
-            if ctx.needs_input_grad[0]:
-                dxs, _ = ops.cheb_backward(plan, dpre.view(T * N, M, 4 * H), None, Wx, K,
-                                           need_dW=False)
-            dx_out = dxs.view(T, N, M, F) if dxs is not None else None
-            if cell.seq:  # raises CGError if the forward's launch lost a pair hand-off
-                ops.lstm_seq_fault(plan, wait=True)
-            return (dx_out, None if zero_init else dc, None if zero_init else dh_rec, dWx, dWh, db,
-                    None, None, None, None)
+            dc, dh_rec, dWh = _bptt_step(cell, dh_at(t), dh_rec, dc, act[t],
+                                         _prev_state(t, zero_init, c0, cs), cs[t], Wh, dpre[t],
+                                         None if cell.fused else hb[t], t >= t_first, lone)
         if T <= t_first:
             dWh = torch.zeros_like(Wh)
-        elif cell.seq:  # one GEMM over the K planes of every step with an h-conv
-            dWh = ops.weight_grad_planes(hb[0, t_first:T].reshape(-1, H), (T + 1) * R * H, K,
-                                         (T - t_first) * R, dpre[t_first:])
-        elif fused:
+        elif cell.fused:
             t0_parts, dparts = [], []
             if t_first == 0:  # step 0 ran its h-conv on h0
                 t0_parts.append(h0.reshape(R, H))
@@ -477,17 +482,32 @@ class _Layer(torch.autograd.Function):
                 dparts.append(dpre[1:T])
             dWh = _hweight_grad_planes(t0_parts, [hb[k, t_first:T] for k in range(K - 1)], dparts,
                                        H, K)
-        else:
+        elif not lone:
             dWh = ops.weight_grad(hb[t_first:], dpre[t_first:])
         dxs, dWx = ops.cheb_backward(plan, dpre.view(T * N, M, 4 * H), basis_x, Wx, K,
                                      need_dx=ctx.needs_input_grad[0])
         db = ops.bias_grad(dpre)
-        dx_out = dxs.view(T, N, M, F) if dxs is not None else None
-        dc0 = None if zero_init else dc
-        dh0 = None if zero_init else dh_rec
-        if cell.seq:  # raises CGError if the forward's launch lost a pair hand-off
-            ops.lstm_seq_fault(plan, wait=True)
-        return dx_out, dc0, dh0, dWx, dWh, db, None, None, None, None
+        return (dxs.view(T, N, M, F) if dxs is not None else None, None if zero_init else dc,
+                None if zero_init else dh_rec, dWx, dWh, db, None, None, None, None)
+
+
+def _bptt_step(cell, dh, dh_rec, dc, act, c_prev, c_out, Wh, dpre, basis_h, h_ran: bool,
+               need_dW: bool):
+    """One BPTT step of _StepLayer: dpre [R, 4H] filled; returns (dc_prev,
+    dh_prev or None if the step ran no h-conv, dWh if need_dW).  A ``cell.seq``
+    cell (a single step of it: its layers are _SeqLayer's) has the one-launch
+    backward step; the others the pointwise kernel plus chebyshev5's backward."""
+    H, K, plan, gates = cell._num_units, cell._K, cell.plan, cell.gates
+    if cell.seq:
+        _, dc_prev, dh_prev = ops.lstm_bwd_step(plan, dh, dh_rec, dc, act, c_prev, c_out, Wh, K,
+                                                gates, out_dpre=dpre, need_dh_prev=h_ran)
+        return dc_prev, dh_prev, None
+    _, dc_prev = ops.lstm_cell_backward(dh, dh_rec, dc, act, c_prev, c_out, H, gates, out_dpre=dpre)
+    if not h_ran:
+        return dc_prev, None, None
+    dh_prev, dWh = ops.cheb_backward(plan, dpre.view(-1, plan.M, 4 * H), basis_h, Wh, K,
+                                     need_dW=need_dW)
+    return dc_prev, dh_prev, dWh
 
 
 class _FourierGates(torch.autograd.Function):
@@ -519,14 +539,6 @@ def _fourier_unfused_step(cell, x, c, h):
     return _FourierGates.apply(gx, gh, cell.b, c, cell._num_units, cell.gates)
 
 
-def _fourier_cell_step(cell, x, c, h):
-    if not cell.fused:
-        return _fourier_unfused_step(cell, x, c, h)
-    _, new_c, new_h = _FourierLayer.apply(x.unsqueeze(0), c.contiguous(), h.contiguous(), cell.Wx,
-                                          cell.Wh, cell.b, cell, False, True)
-    return new_c, new_h
-
-
 class _FourierLayer(torch.autograd.Function):
     """static_rnn of one Fourier cell over a [T, N, M, F] sequence (a single
     cell step is T = 1).  Forward: ONE analysis of all T*N inputs, ONE
@@ -538,8 +550,7 @@ class _FourierLayer(torch.autograd.Function):
     and dWx are ONE weight-gradient launch each over the stacked steps."""
 
     @staticmethod
-    def forward(ctx, xs, c0, h0, Wx, Wh, b, cell: GConvLSTMCell, zero_init: bool,
-                want_c: bool = True):
+    def forward(ctx, xs, c0, h0, Wx, Wh, b, cell: GConvLSTMCell, zero_init: bool, want_c: bool):
         H, gates, basis = cell._num_units, cell.gates, cell.gft_basis
         xs = xs.contiguous()
         T, N, M, F = xs.shape
@@ -551,15 +562,13 @@ class _FourierLayer(torch.autograd.Function):
         act = torch.empty((T, N, M, 4 * H), **f32)
         hhat = torch.empty((T, N, M, H), **f32)  # U^T h_{t-1}: the weight gradient's operand
         for t in range(T):
-            h_prev = (None if zero_init else h0) if t == 0 else hs[t - 1]
-            c_prev = (None if zero_init else c0) if t == 0 else cs[t - 1]
-            ops.flstm_step(basis, h_prev, c_prev, ghx[t], Wh, b, gates, out_c=cs[t], out_h=hs[t],
-                           out_act=act[t], out_hhat=hhat[t])
+            ops.flstm_step(basis, _prev_state(t, zero_init, h0, hs), _prev_state(t, zero_init, c0, cs),
+                           ghx[t], Wh, b, gates, out_c=cs[t], out_h=hs[t], out_act=act[t],
+                           out_hhat=hhat[t])
         ctx.save_for_backward(xhat, hhat, Wx, Wh, act, cs, c0)
         ctx.cell, ctx.zero_init, ctx.shape = cell, zero_init, (T, N, M, F)
         ctx.set_materialize_grads(False)
-        cT = cs[T - 1].clone() if want_c else cs.new_empty(0)
-        return hs, cT, hs[T - 1].clone()
+        return hs, _final_c(ctx, cs, want_c), hs[T - 1].clone()
 
     @staticmethod
     def backward(ctx, dhs, dcT, dhT):
@@ -570,21 +579,13 @@ class _FourierLayer(torch.autograd.Function):
         f32 = dict(device=act.device, dtype=torch.float32)
         dpre = torch.empty((T, N, M, 4 * H), **f32)
         dghat = torch.empty((T, N, M, 4 * H), **f32)
-        dhs = dhs.contiguous() if dhs is not None else None
-        dc = dcT.contiguous() if dcT is not None else None
-        dh_last = None  # the gradient of h_{T-1}: through hs and through h_T
-        if dhT is not None:
-            dh_last = dhT.contiguous() if dhs is None else dhs[T - 1] + dhT
-        elif dhs is not None:
-            dh_last = dhs[T - 1]
+        dc, dh_at = _bptt_grads(dhs, dcT, dhT, T)
         dh_rec = None
         t_first = 1 if zero_init else 0  # first step whose h part ran
         dhhat = torch.empty((N, M, H), **f32)
         for t in range(T - 1, -1, -1):
-            c_prev = (None if zero_init else c0) if t == 0 else cs[t - 1]
-            dh_t = dh_last if t == T - 1 else (None if dhs is None else dhs[t])
-            _, dc = ops.lstm_cell_backward(dh_t, dh_rec, dc, act[t], c_prev, cs[t], H, gates,
-                                           out_dpre=dpre[t])
+            _, dc = ops.lstm_cell_backward(dh_at(t), dh_rec, dc, act[t], _prev_state(t, zero_init, c0, cs),
+                                           cs[t], H, gates, out_dpre=dpre[t])
             ops.gft(basis, dpre[t], out=dghat[t])  # a = U ghat  ->  d ghat = U^T dpre
             if t >= t_first:
                 ops.fourier_mix("t", Wh, g=dghat[t], out=dhhat)
@@ -605,26 +606,14 @@ class _FourierLayer(torch.autograd.Function):
                 None, None, None)
 
 
-def _fourier_layer(cell, xs, initial_state, final_c):
-    """layer() for a Fourier cell."""
-    if not cell.fused:  # the composition, step by step under autograd
-        if initial_state is None:
-            c, h = cell.zero_state(xs.shape[1])
-        else:
-            c, h = initial_state
-        outs = []
-        for t in range(xs.shape[0]):
-            c, h = _fourier_unfused_step(cell, xs[t], c, h)
-            outs.append(h)
-        return torch.stack(outs), LSTMStateTuple(c if final_c else c.new_empty(0), h)
-    if initial_state is None:
-        z = xs.new_empty(0)
-        hs, cT, hT = _FourierLayer.apply(xs, z, z, cell.Wx, cell.Wh, cell.b, cell, True, final_c)
-    else:
-        c0, h0 = initial_state
-        hs, cT, hT = _FourierLayer.apply(xs, c0.contiguous(), h0.contiguous(), cell.Wx, cell.Wh,
-                                         cell.b, cell, False, final_c)
-    return hs, LSTMStateTuple(cT, hT)
+def _fourier_unfused_layer(cell, xs, initial_state, final_c):
+    """layer() for the unfused Fourier cell: the composition, step by step under autograd."""
+    c, h = cell.zero_state(xs.shape[1]) if initial_state is None else initial_state
+    outs = []
+    for t in range(xs.shape[0]):
+        c, h = _fourier_unfused_step(cell, xs[t], c, h)
+        outs.append(h)
+    return torch.stack(outs), LSTMStateTuple(c if final_c else c.new_empty(0), h)
 
 
 class DropoutWrapper:
@@ -680,18 +669,23 @@ def layer(cell, xs: torch.Tensor, initial_state=None, final_c: bool = True):
     if isinstance(cell, DropoutWrapper):
         hs, state = layer(cell.cell, xs, initial_state, final_c)
         return ops.dropout(hs, cell.output_keep_prob, cell.next_seed()), state
-    if cell.filter_type == "fourier_conv":
-        return _fourier_layer(cell, xs, initial_state, final_c)
-    ins = [xs, cell.Wx, cell.Wh, cell.b] + ([] if initial_state is None else list(initial_state))
-    check_now = not (torch.is_grad_enabled() and any(t.requires_grad for t in ins))
-    if initial_state is None:
-        z = xs.new_empty(0)  # placeholders: a zero state is never read (no fill launch)
-        hs, cT, hT = _Layer.apply(xs, z, z, cell.Wx, cell.Wh, cell.b, cell, True, check_now,
-                                  final_c)
+    fourier = cell.filter_type == "fourier_conv"
+    if fourier and not cell.fused:
+        return _fourier_unfused_layer(cell, xs, initial_state, final_c)
+    zero_init = initial_state is None
+    if zero_init:
+        c0 = h0 = xs.new_empty(0)  # placeholders: a zero state is never read (no fill launch)
     else:
-        c0, h0 = initial_state
-        hs, cT, hT = _Layer.apply(xs, c0.contiguous(), h0.contiguous(), cell.Wx, cell.Wh, cell.b,
-                                  cell, False, check_now, final_c)
+        c0, h0 = (s.contiguous() for s in initial_state)
+    args = (xs, c0, h0, cell.Wx, cell.Wh, cell.b, cell, zero_init, final_c)
+    if fourier:
+        hs, cT, hT = _FourierLayer.apply(*args)
+    elif cell.seq:
+        # nobody will call a backward: the sequence launch is checked before returning
+        check_now = not (torch.is_grad_enabled() and any(t.requires_grad for t in args[:6]))
+        hs, cT, hT = _SeqLayer.apply(*args, check_now)
+    else:
+        hs, cT, hT = _StepLayer.apply(*args, False)
     return hs, LSTMStateTuple(cT, hT)
 
 

@@ -664,27 +664,13 @@ def lstm_seq_fault(plan: ChebPlan, wait: bool = True) -> bool | None:
     return None if f.value < 0 else False
 
 
-def lstm_seq_forward(plan: ChebPlan, gx, Wh, bias, K: int, T: int, N: int, gates="reference",
-                     h0=None, c0=None, out_hs=None, out_cs=None, out_act=None, planes=None,
-                     plane_stride: int = 0, check: bool = False):
-    """All T steps of a gconv-LSTM layer in ONE launch (cg_lstm_seq_forward):
-    gx [T, N, M, 4H] (the x-conv of every step), h0 / c0 [N, M, H] or None
-    (zero state).  planes (optional; a tensor whose storage holds K-1 planes
-    [T, N, M, H] plane_stride floats apart) receives T_k of h_{t-1}, k >= 1.
-    check=True waits for the launch and raises CGError if a pair hand-off timed
-    out (lstm_seq_fault); without it the fault surfaces at the next check.
-    Returns (hs [T, N, M, H], cs [T, N, M, H], act or None) -- act UNIT-major,
-    [T, N, M, 4H] holding act[..., 4u + g] (g = z, i, f, o): lstm_bwd_step
-    reads it with act_unit_major=True."""
-    _check_dev("gx", gx)
-    H = int(Wh.shape[1]) // 4
-    M = plan.M
+def _lstm_seq_prepare(plan: ChebPlan, dev, T: int, N: int, M: int, H: int, K: int, bias, h0, c0,
+                      out_hs, out_cs, out_act, planes, plane_stride: int):
+    """What lstm_seq_forward and lstm_seq_forward_x share: the bias / state
+    checks, the hs / cs outputs (allocated unless given), the act check, the
+    K-1 h planes (allocated unless given) and the launch's workspace.
+    Returns (hs, cs, planes, plane_stride, workspace)."""
     R = T * N * M
-    if not gx.is_contiguous() or gx.numel() != R * 4 * H:
-        raise ValueError(f"gx must be a contiguous [{T}, {N}, {M}, {4 * H}] tensor")
-    if tuple(Wh.shape) != (K * H, 4 * H) or not Wh.is_contiguous():
-        raise ValueError(f"Wh must be a contiguous [{K * H}, {4 * H}] tensor")
-    dev = gx.device
     for name, t, n in (("bias", bias, 4 * H), ("h0", h0, N * M * H), ("c0", c0, N * M * H)):
         if t is not None:
             _check_dev(name, t)
@@ -709,11 +695,36 @@ def lstm_seq_forward(plan: ChebPlan, gx, Wh, bias, K: int, T: int, N: int, gates
             raise ValueError("planes: storage too small / misaligned for the K-1 planes")
     nb = ctypes.c_size_t()
     _lib.call("cg_lstm_seq_workspace_bytes", plan.handle, int(N), ctypes.byref(nb))
-    ws = torch.empty(int(nb.value), device=dev, dtype=torch.uint8)
+    return hs, cs, planes, plane_stride, torch.empty(int(nb.value), device=dev, dtype=torch.uint8)
+
+
+def lstm_seq_forward(plan: ChebPlan, gx, Wh, bias, K: int, T: int, N: int, gates="reference",
+                     h0=None, c0=None, out_hs=None, out_cs=None, out_act=None, planes=None,
+                     plane_stride: int = 0, check: bool = False):
+    """All T steps of a gconv-LSTM layer in ONE launch (cg_lstm_seq_forward):
+    gx [T, N, M, 4H] (the x-conv of every step), h0 / c0 [N, M, H] or None
+    (zero state).  planes (optional; a tensor whose storage holds K-1 planes
+    [T, N, M, H] plane_stride floats apart) receives T_k of h_{t-1}, k >= 1.
+    check=True waits for the launch and raises CGError if a pair hand-off timed
+    out (lstm_seq_fault); without it the fault surfaces at the next check.
+    Returns (hs [T, N, M, H], cs [T, N, M, H], act or None) -- act UNIT-major,
+    [T, N, M, 4H] holding act[..., 4u + g] (g = z, i, f, o): lstm_bwd_step
+    reads it with act_unit_major=True."""
+    _check_dev("gx", gx)
+    H = int(Wh.shape[1]) // 4
+    M = plan.M
+    R = T * N * M
+    if not gx.is_contiguous() or gx.numel() != R * 4 * H:
+        raise ValueError(f"gx must be a contiguous [{T}, {N}, {M}, {4 * H}] tensor")
+    if tuple(Wh.shape) != (K * H, 4 * H) or not Wh.is_contiguous():
+        raise ValueError(f"Wh must be a contiguous [{K * H}, {4 * H}] tensor")
+    hs, cs, planes, plane_stride, ws = _lstm_seq_prepare(plan, gx.device, T, N, M, H, K, bias, h0,
+                                                         c0, out_hs, out_cs, out_act, planes,
+                                                         plane_stride)
     s = _stream(gx)
     _lib.call("cg_lstm_seq_forward", plan.handle, int(T), int(N), int(H), int(K), LSTM_GATES[gates],
               _p(gx), _p(Wh), _p(bias), _p(h0), _p(c0), _p(hs), _p(cs), _p(out_act), _p(planes),
-              int(plane_stride), _p(ws), int(nb.value), s)
+              int(plane_stride), _p(ws), ws.numel(), s)
     if check:
         lstm_seq_fault(plan, wait=True)
     return hs, cs, out_act
@@ -738,42 +749,20 @@ def lstm_seq_forward_x(plan: ChebPlan, xs, Wx, Wh, bias, K: int, gates="referenc
     H = int(Wh.shape[1]) // 4
     R = T * N * M
     dev = xs.device
-    f32 = dict(device=dev, dtype=torch.float32)
     if tuple(Wx.shape) != (K * F, 4 * H) or not Wx.is_contiguous():
         raise ValueError(f"Wx must be a contiguous [{K * F}, {4 * H}] tensor")
     if tuple(Wh.shape) != (K * H, 4 * H) or not Wh.is_contiguous():
         raise ValueError(f"Wh must be a contiguous [{K * H}, {4 * H}] tensor")
-    for name, t, n in (("bias", bias, 4 * H), ("h0", h0, N * M * H), ("c0", c0, N * M * H)):
-        if t is not None:
-            _check_dev(name, t)
-            if not t.is_contiguous() or t.numel() != n or t.data_ptr() % 16:
-                raise ValueError(f"{name}: need a contiguous 16-byte aligned tensor of {n} floats")
-    hs = out_hs if out_hs is not None else torch.empty((T, N, M, H), **f32)
-    cs = out_cs if out_cs is not None else torch.empty((T, N, M, H), **f32)
-    _check_out("hs", hs, (R, H))
-    _check_out("cs", cs, (R, H))
-    if out_act is not None:
-        _check_out("act", out_act, (R, 4 * H))
-    if planes is None and K > 1:
-        planes = torch.empty((K - 1, R, H), **f32)
-        plane_stride = R * H
-    if planes is not None:
-        _check_dev("planes", planes)
-        need = (K - 2) * plane_stride + R * H if K > 1 else 0
-        avail = planes.untyped_storage().nbytes() // 4 - planes.storage_offset()
-        if K > 1 and (plane_stride < R * H or avail < need or planes.data_ptr() % 16
-                      or plane_stride % 4):
-            raise ValueError("planes: storage too small / misaligned for the K-1 planes")
+    hs, cs, planes, plane_stride, ws = _lstm_seq_prepare(plan, dev, T, N, M, H, K, bias, h0, c0,
+                                                         out_hs, out_cs, out_act, planes,
+                                                         plane_stride)
     if xplanes is None:
-        xplanes = torch.empty((K, R, F), **f32)
+        xplanes = torch.empty((K, R, F), device=dev, dtype=torch.float32)
     _check_out("xplanes", xplanes, (K * R * F,))
-    nb = ctypes.c_size_t()
-    _lib.call("cg_lstm_seq_workspace_bytes", plan.handle, int(N), ctypes.byref(nb))
-    ws = torch.empty(int(nb.value), device=dev, dtype=torch.uint8)
     s = _stream(xs)
     _lib.call("cg_lstm_seq_forward_x", plan.handle, T, N, F, int(H), int(K), LSTM_GATES[gates],
               _p(xs), _p(Wx), _p(xplanes), R * F, _p(Wh), _p(bias), _p(h0), _p(c0), _p(hs), _p(cs),
-              _p(out_act), _p(planes), int(plane_stride), _p(ws), int(nb.value), s)
+              _p(out_act), _p(planes), int(plane_stride), _p(ws), ws.numel(), s)
     if check:
         lstm_seq_fault(plan, wait=True)
     return hs, cs, out_act, xplanes

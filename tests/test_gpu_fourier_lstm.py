@@ -217,6 +217,29 @@ def test_fused_layer_on_the_grid_graph(dev, x3):
     _run_layers(dev, "E", T=2, N=2, Fin=2, H=32, layers=1, given_state=False, seed=31)
 
 
+def test_layer_without_final_c(dev):
+    """layer(..., final_c=False): an empty c_T that autograd does not
+    differentiate, and the gradients of the final_c=True call, bitwise."""
+    from cnn_graph_amd.gconv_lstm import layer
+    cell = make_cell("A", 2, 32, "reference", dev, seed=41, hconv="fused")
+    assert cell.fused
+    g = torch.Generator(device=dev)
+    g.manual_seed(4)
+    xs = torch.randn((3, 2, cell._nNode, 2), device=dev, generator=g)
+    grads = {}
+    for final_c in (True, False):
+        for p in cell.parameters():
+            p.grad = None
+        hs, state = layer(cell, xs, final_c=final_c)
+        if not final_c:
+            assert state.c.numel() == 0 and state.c.requires_grad is False
+        hs.sum().backward()
+        grads[final_c] = [p.grad.clone() for p in cell.parameters()]
+    torch.cuda.synchronize()
+    for a, b in zip(grads[True], grads[False]):
+        assert int(torch.count_nonzero(a)) > 0 and torch.equal(a, b)
+
+
 # -- the model ---------------------------------------------------------------------------
 def test_glstm_model_fourier_train_step(dev, x3):
     from cnn_graph_amd.gconv_lstm import GLSTMModel

@@ -120,14 +120,19 @@ def test_weight_and_bias_grad_accumulate(dev):
 
 
 @pytest.mark.parametrize("gates", ["reference", "standard"])
-@pytest.mark.parametrize("H,K", [(8, 3), (32, 3), (32, 2), (32, 4)])
-def test_cell_step_autograd_vs_oracle(dev, gates, H, K):
+@pytest.mark.parametrize("H,K,hconv", [(8, 3, "auto"), (32, 3, "auto"), (32, 2, "auto"), (32, 4, "auto"),
+                                       (32, 3, "fused"), (32, 3, "unfused")],
+                         ids=["8-3", "32-3", "32-2", "32-4", "32-3-fused", "32-3-unfused"])
+def test_cell_step_autograd_vs_oracle(dev, gates, H, K, hconv):
     """GConvLSTMCell.__call__ with a non-zero state, gradients by autograd
-    (H = 32: the one-launch h-step, cg_lstm_hconv_step)."""
+    (H = 32: the one-launch h-step, cg_lstm_hconv_step).  At H = 32, K = 3 the
+    three resolutions of hconv: "auto" (a .seq cell: the one-launch backward
+    step), "fused" (pointwise backward + chebyshev5) and "unfused"."""
     Lt, _, M = graph_E()
     N, Fin = 3, 2
-    cell, L = make_cell(Lt, Fin, H, K, gates, dev, seed=11)
-    assert cell.fused == (H == 32)
+    cell, L = make_cell(Lt, Fin, H, K, gates, dev, seed=11, hconv=hconv)
+    assert cell.fused == (H == 32 and hconv != "unfused")
+    assert cell.seq == (H == 32 and hconv == "auto")
     lap = oracle_lap(cell, L)
     rng = np.random.default_rng(2)
     x, c0, h0 = rng.standard_normal((N, M, Fin)), rng.standard_normal((N, M, H)) * 0.5, \
@@ -533,3 +538,115 @@ def test_seq_handoff_timeout_raises_and_poisons(dev):
     with torch.no_grad():
         again, _ = layer(cell, xs)
     assert torch.equal(again, ref)
+
+
+# -- layers at the sizes where the paths of layer() part ----------------------------------
+_LAYER_REFS = {}
+
+
+def _run_layer(dev, hconv, H, K, T, given):
+    """layer() of one cell (seed 71) on graph_E() at N = 3, Fin = 2, forward and
+    backward of sum(hs * gh) + sum(c_T * gc).
+    Returns (cell, state tensors or None, device inputs, outputs and gradients
+    by name, the same from the float64 oracle).  The weights and inputs depend
+    on (H, K, T, given) only, so the hconv modes of one shape share one oracle run."""
+    from cnn_graph_amd.gconv_lstm import layer
+    Lt, _, M = graph_E()
+    N, Fin = 3, 2
+    cell, L = make_cell(Lt, Fin, H, K, "reference", dev, seed=71, hconv=hconv)
+    rng = np.random.default_rng(1000 * H + 10 * T + K)
+    xs = rng.standard_normal((T, N, M, Fin))
+    c0, h0 = (rng.standard_normal((N, M, H)) * 0.5 for _ in range(2))
+    gh, gc = rng.standard_normal((T, N, M, H)), rng.standard_normal((N, M, H))
+    xt = t(xs, dev).requires_grad_()
+    st = tuple(t(a, dev).requires_grad_() for a in (c0, h0)) if given else None
+    hs, state = layer(cell, xt, st)
+    ((hs * t(gh, dev)).sum() + (state.c * t(gc, dev)).sum()).backward()
+    torch.cuda.synchronize()
+    got = dict(hs=hs.detach(), c_T=state.c.detach(), h_T=state.h.detach(), dx=xt.grad,
+               dWx=cell.Wx.grad.clone(), dWh=cell.Wh.grad.clone(), db=cell.b.grad.clone())
+    if given:
+        got.update(dc0=st[0].grad, dh0=st[1].grad)
+    key = (H, K, T, given)
+    p = params_np(cell)
+    if key not in _LAYER_REFS:
+        f32 = lambda a: a.astype(np.float32).astype(np.float64)  # noqa: E731
+        lap = oracle_lap(cell, L)
+        s0 = (f32(c0), f32(h0)) if given else (None, None)
+        r_hs, r_cs, caches = LO.layer_forward(f32(xs), p, lap, K, H, *s0)
+        dxs, dc0, dh0, dWx, dWh, db = LO.layer_backward(f32(gh), f32(gc), caches, p, lap, K, H)
+        _LAYER_REFS[key] = (p, dict(hs=r_hs, c_T=r_cs[-1], h_T=r_hs[-1], dx=dxs, dc0=dc0, dh0=dh0,
+                                    dWx=dWx, dWh=dWh, db=db))
+    p_ref, ref = _LAYER_REFS[key]
+    assert all(np.array_equal(a, b) for a, b in zip(p, p_ref))  # the same seeded weights
+    return cell, st, (xt, t(gh, dev), t(gc, dev)), got, ref
+
+
+def _check_vs_oracle(got, ref, names):
+    for name in names:
+        err = O.normwise_err(got[name].cpu().numpy(), ref[name])
+        print(f"{name}: normwise err {err:.3e}")
+        assert err < TOL, (name, err)
+
+
+@pytest.mark.parametrize("given", [False, True], ids=["zero_state", "given_state"])
+@pytest.mark.parametrize("hconv,H", [("seq", 32), ("fused", 32), ("unfused", 32), ("unfused", 8)])
+def test_single_step_layer_vs_oracle(dev, hconv, H, given):
+    """layer() at T = 1 (K = 3), where a layer is one cell step.  Zero state:
+    no h-conv runs, so dWh is exactly zero.  Given state: every gradient
+    against the oracle, and for the stepping paths ("fused", "unfused") the
+    layer and cell(x, state) are one code path: bitwise-equal results."""
+    K = 3
+    cell, st, (xt, gh, gc), got, ref = _run_layer(dev, hconv, H, K, 1, given)
+    assert cell.seq == (hconv == "seq") and cell.fused == (hconv != "unfused")
+    if not given:
+        _check_vs_oracle(got, ref, ["hs", "c_T", "dWx", "db"])
+        assert int(torch.count_nonzero(got["dWh"])) == 0
+        return
+    _check_vs_oracle(got, ref, ["hs", "c_T", "dx", "dc0", "dh0", "dWx", "dWh", "db"])
+    if hconv == "seq":  # its single step is another kernel than its layer
+        return
+    for a in (xt, *st, *cell.parameters()):
+        a.grad = None
+    new_h, (new_c, _) = cell(xt[0], st)
+    ((new_h * gh[0]).sum() + (new_c * gc).sum()).backward()
+    torch.cuda.synchronize()
+    step = dict(hs=new_h.detach().unsqueeze(0), c_T=new_c.detach(), dx=xt.grad, dc0=st[0].grad,
+                dh0=st[1].grad, dWx=cell.Wx.grad, dWh=cell.Wh.grad, db=cell.b.grad)
+    for name, a in step.items():
+        assert torch.equal(a, got[name]), name
+
+
+@pytest.mark.parametrize("given", [False, True], ids=["zero_state", "given_state"])
+@pytest.mark.parametrize("hconv", ["seq", "fused"])
+def test_order_one_layer_vs_oracle(dev, hconv, given):
+    """K = 1 at T = 3: no Chebyshev planes at all (the sequence kernel gets
+    planes=None, the fused h-step a plane buffer it never writes)."""
+    cell, st, _, got, ref = _run_layer(dev, hconv, 32, 1, 3, given)
+    assert cell.seq == (hconv == "seq")
+    _check_vs_oracle(got, ref, ["hs", "c_T", "h_T", "dx", "dWx", "dWh", "db"] +
+                     (["dc0", "dh0"] if given else []))
+
+
+def test_layer_without_final_c(dev):
+    """layer(..., final_c=False): an empty c_T that autograd does not
+    differentiate, and the gradients of the final_c=True call, bitwise."""
+    from cnn_graph_amd.gconv_lstm import layer
+    Lt, _, M = graph_E()
+    T, N, Fin, H, K = 3, 3, 2, 32, 3
+    cell, _ = make_cell(Lt, Fin, H, K, "reference", dev, seed=81)
+    g = torch.Generator(device=dev)
+    g.manual_seed(4)
+    xs = torch.randn((T, N, M, Fin), device=dev, generator=g)
+    grads = {}
+    for final_c in (True, False):
+        for p in cell.parameters():
+            p.grad = None
+        hs, state = layer(cell, xs, final_c=final_c)
+        if not final_c:
+            assert state.c.numel() == 0 and state.c.requires_grad is False
+        hs.sum().backward()
+        grads[final_c] = [p.grad.clone() for p in cell.parameters()]
+    torch.cuda.synchronize()
+    for a, b in zip(grads[True], grads[False]):
+        assert int(torch.count_nonzero(a)) > 0 and torch.equal(a, b)
