@@ -27,21 +27,29 @@ def _sigmoid(a):
     return 1.0 / (1.0 + np.exp(-a))
 
 
-def cell_forward(x, c, h, Wx, Wh, b, U, gates="reference"):
-    """One step (lib/gconv_lstm.py:183-221).  Returns (c', h', cache); the
-    cache holds ``az`` (the z pre-activation, for the tan pole guard)."""
-    H = Wh.shape[2]
-    gx, xhat = FO.fourier_forward(x, Wx, U)
-    gh, hhat = FO.fourier_forward(h, Wh, U)
-    a = gx + gh + np.asarray(b, np.float64)                       # (:186-187 ...)
+def gate_update(a, c, gates="reference"):
+    """The gate algebra (lib/gconv_lstm.py:188-218) on the pre-activations
+    a [..., 4H] (z, i, f, o along the last axis) and the state c [..., H].
+    Returns (c', h', dict of z, i, f, o, az)."""
+    H = a.shape[-1] // 4
     az, ai, af, ao = (a[..., q * H:(q + 1) * H] for q in range(4))
     z = np.tan(az) if gates == "reference" else np.tanh(az)       # (:188)
     i, f = _sigmoid(ai), _sigmoid(af)                             # (:195, :202)
     o = np.tanh(ao) if gates == "reference" else _sigmoid(ao)     # (:209)
-    c = np.asarray(c, np.float64)
     cn = f * c + i * z                                            # (:215)
     hn = o * np.tanh(cn)                                          # (:218)
-    cache = dict(c=c, cn=cn, z=z, i=i, f=f, o=o, xhat=xhat, hhat=hhat, az=az)
+    return cn, hn, dict(z=z, i=i, f=f, o=o, az=az)
+
+
+def cell_forward(x, c, h, Wx, Wh, b, U, gates="reference"):
+    """One step (lib/gconv_lstm.py:183-221).  Returns (c', h', cache); the
+    cache holds ``az`` (the z pre-activation, for the tan pole guard)."""
+    gx, xhat = FO.fourier_forward(x, Wx, U)
+    gh, hhat = FO.fourier_forward(h, Wh, U)
+    a = gx + gh + np.asarray(b, np.float64)                       # (:186-187 ...)
+    c = np.asarray(c, np.float64)
+    cn, hn, g = gate_update(a, c, gates)
+    cache = dict(c=c, cn=cn, xhat=xhat, hhat=hhat, **g)
     return cn, hn, cache
 
 

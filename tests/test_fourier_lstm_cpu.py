@@ -1,10 +1,13 @@
 """gconv-LSTM with the Fourier filter, the parts that need no GPU: the float64
 restatement (tests/fourier_lstm_ref.py) pinned to itself by finite differences
-and to a vertex-domain filter, and the new C-ABI entry points' argument checks."""
+and to a vertex-domain filter, the premises of the tile-edge GPU tests' inputs
+(tests/fourier_edge_cases.py), and the new C-ABI entry points' argument checks."""
 import ctypes
 
 import numpy as np
+import pytest
 
+import fourier_edge_cases as FE
 import fourier_lstm_ref as FR
 from cnn_graph_amd import _lib
 
@@ -77,6 +80,63 @@ def test_restatement_equals_a_vertex_domain_filter():
     c_ref = f * c0 + i * z
     assert np.abs(cn - c_ref).max() < 1e-12 * max(1.0, np.abs(c_ref).max())
     assert np.abs(hn - o * np.tanh(c_ref)).max() < 1e-12
+
+
+# -- what tests/test_gpu_fourier_edges.py rests on ---------------------------------------
+@pytest.mark.parametrize("M,N,C", FE.TRANSFORM_SHAPES)
+def test_edge_transform_operands_are_exact_in_float32(M, N, C):
+    """Integers of at most 4 bits (no mid or lo term in the bf16 split), every
+    partial sum below 2^24, and a U that tells U from U^T."""
+    U, x = FE.int_transform_case(M, N, C)
+    assert U.shape == (M, M) and x.shape == (N, M, C)
+    assert FE.exact_bound(U, x, depth=M) < 2 ** 24
+    assert 64 * M < 2 ** 24
+    if M > 1:
+        assert not np.array_equal(FE.transform_ref(U, x, False), FE.transform_ref(U, x, True))
+
+
+@pytest.mark.parametrize("R,M,Cin,Cout", FE.MIX_SHAPES)
+def test_edge_mix_operands_are_exact_in_float32(R, M, Cin, Cout):
+    c = FE.int_mix_case(R, M, Cin, Cout)
+    assert FE.exact_bound(*c.values(), depth=max(R, Cin, Cout)) < 2 ** 24
+    assert 64 * max(M, R, Cin, Cout) < 2 ** 24
+    for k, ref in FE.mix_refs(c).items():  # and the float64 einsums themselves are exact integers
+        assert np.array_equal(ref, np.rint(ref)) and np.abs(ref).max() < 2 ** 24, k
+
+
+def test_edge_split_operands():
+    """The permutation and one-hot cases: one non-zero product per output, and
+    operands with full significands (a lo term to lose)."""
+    p, U, x = FE.permutation_case()
+    assert np.array_equal(U.sum(0), np.ones(len(p))) and np.array_equal(U.sum(1), np.ones(len(p)))
+    assert not np.array_equal(p, np.argsort(p))  # p is not its own inverse: U and U^T differ
+    assert np.array_equal(FE.transform_ref(U, x, False), x[:, p, :])
+    U2, x2, at = FE.one_hot_case()
+    assert np.array_equal(x2.sum(1), np.ones(at.shape)) and np.array_equal(np.unique(x2), [0.0, 1.0])
+    for a in (x, U2):  # nearly every value needs the third bf16 term
+        bits = np.asarray(a, np.float32).view(np.uint32)
+        assert np.mean((bits & 0xff) != 0) > 0.9
+
+
+@pytest.mark.parametrize("given_state", [False, True])
+@pytest.mark.parametrize("M,N,H", FE.STEP_SHAPES)
+def test_edge_step_inputs_clear_the_pole(M, N, H, given_state):
+    c = FE.step_case(M, N, H)
+    assert np.abs(c["U"].T @ c["U"] - np.eye(M)).max() < 1e-6  # orthogonal, as float32 values
+    ref = FE.step_ref(c, "reference", given_state)
+    assert np.abs(ref["az"]).max() < FE.AZ_MAX
+    assert all(np.isfinite(v).all() for v in ref.values() if v is not None)
+
+
+@pytest.mark.parametrize("given_state", [False, True])
+def test_edge_layer_inputs_clear_the_pole(given_state):
+    from cnn_graph_amd import graph
+    L, M = FE.synthetic_laplacian(FE.LAYER_GRAPH)
+    assert L.shape == (M, M) and M == 130 and abs(L - L.T).max() < 1e-6
+    U = FR.r32(graph.fourier(L)[1])  # what filter.fourier_basis puts on the device
+    inp = FE.layer_inputs(given_state, M=M, **FE.LAYER_CASE)
+    for hs, cs, caches in FE.layers_forward(inp, U, "reference"):
+        assert FR.max_az(caches) < FE.AZ_MAX
 
 
 def test_header_declares_the_fourier_lstm_entry_points(built_lib):

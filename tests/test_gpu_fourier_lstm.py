@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import scipy.sparse
 
+import fourier_edge_cases as FE
 import fourier_lstm_ref as FR
 from conftest import case, load_golden
 from oracle import cheb_oracle as O
@@ -47,8 +48,11 @@ def npy(a):
 
 @functools.lru_cache(maxsize=None)
 def laplacian(name):
-    """The golden graph's Laplacian L = L~ + I (lmax = 2), kept per name so the
-    cells of a test share one cached Fourier basis."""
+    """The Laplacian L = L~ + I (lmax = 2) of a golden graph, or of one of
+    fourier_edge_cases' synthetic k-NN graphs, kept per name so the cells of a
+    test share one cached Fourier basis."""
+    if name in FE.SYNTHETIC_GRAPHS:
+        return FE.synthetic_laplacian(name)
     c = case(load_golden(f"golden_{name}.npz"))
     M = c["M"]
     Lt = scipy.sparse.csr_matrix((c["Lt_val"], c["Lt_col"], c["Lt_rowptr"]), shape=(M, M))
@@ -64,13 +68,20 @@ def basis(name, dev):
     return U, npy(U).astype(np.float64), ops.gft_prepare(U)
 
 
-def make_cell(name, feat_in, H, gates, dev, seed, hconv="auto"):
+def make_cell(name, feat_in, H, gates, dev, seed, hconv="auto", params=None):
+    """A Fourier cell on the graph `name`; params = (Wx, Wh, b) replaces the
+    seeded initial values (inputs that a test without a GPU can rebuild)."""
     from cnn_graph_amd.gconv_lstm import GConvLSTMCell
     L, M = laplacian(name)
     g = torch.Generator(device=dev)
     g.manual_seed(seed)
-    return GConvLSTMCell(H, laplacian=L, lmax=2, K=3, feat_in=feat_in, gates=gates, device=dev,
+    cell = GConvLSTMCell(H, laplacian=L, lmax=2, K=3, feat_in=feat_in, gates=gates, device=dev,
                          generator=g, hconv=hconv, filter_type="fourier_conv")
+    if params is not None:
+        with torch.no_grad():
+            for p, v in zip(cell.parameters(), params):
+                p.copy_(t(v, dev).view_as(p))
+    return cell
 
 
 def params_np(cell):
@@ -161,21 +172,27 @@ def test_cell_step_autograd_vs_restatement(dev, x3, H, gates, hconv):
 
 
 # -- layers -----------------------------------------------------------------------------
-def _run_layers(dev, name, T, N, Fin, H, layers, given_state, seed):
+def _run_layers(dev, name, T, N, Fin, H, layers, given_state, seed, gates="reference", inputs=None):
     """static_rnn over `layers` Fourier cells against the restatement: outputs,
-    every layer's c_T and every gradient."""
+    every layer's c_T and every gradient.  inputs = fourier_edge_cases.layer_inputs
+    gives the parameters and the data; None draws them here from `seed`."""
     from cnn_graph_amd.gconv_lstm import static_rnn
-    cells = [make_cell(name, Fin if li == 0 else H, H, "reference", dev, seed=seed + li)
+    cells = [make_cell(name, Fin if li == 0 else H, H, gates, dev, seed=seed + li,
+                       params=None if inputs is None else inputs["params"][li])
              for li in range(layers)]
     assert all(c.fused for c in cells)
     M = cells[0]._nNode
     U64 = npy(cells[0].U).astype(np.float64)
-    rng = np.random.default_rng(seed)
-    xs = r32(rng.standard_normal((T, N, M, Fin)))
-    G = r32(rng.standard_normal((T, N, M, H)))
-    GC = r32(rng.standard_normal((layers, N, M, H)))
-    st = [(r32(0.5 * rng.standard_normal((N, M, H))), r32(0.5 * rng.standard_normal((N, M, H))))
-          for _ in range(layers)] if given_state else None
+    if inputs is None:
+        rng = np.random.default_rng(seed)
+        xs = r32(rng.standard_normal((T, N, M, Fin)))
+        G = r32(rng.standard_normal((T, N, M, H)))
+        GC = r32(rng.standard_normal((layers, N, M, H)))
+        st = [(r32(0.5 * rng.standard_normal((N, M, H))), r32(0.5 * rng.standard_normal((N, M, H))))
+              for _ in range(layers)] if given_state else None
+    else:
+        xs, G, GC, st = (inputs[k] for k in ("xs", "G", "GC", "st"))
+        assert xs.shape == (T, N, M, Fin) and G.shape == (T, N, M, H) and (st is not None) == given_state
     xt = t(xs, dev).requires_grad_()
     st_t = None if st is None else [tuple(t(a, dev).requires_grad_() for a in s) for s in st]
     outs, states = static_rnn(cells, xt, st_t)
@@ -188,8 +205,9 @@ def _run_layers(dev, name, T, N, Fin, H, layers, given_state, seed):
     inp, fw = xs, []
     for li in range(layers):
         c0, h0 = (None, None) if st is None else st[li]
-        hs, cs, caches = FR.layer_forward(inp, P[li], U64, c0, h0)
-        assert FR.max_az(caches) < 1.3
+        hs, cs, caches = FR.layer_forward(inp, P[li], U64, c0, h0, gates)
+        if gates == "reference":
+            assert FR.max_az(caches) < 1.3
         fw.append((hs, cs, caches))
         inp = hs
     check("outputs", torch.stack(outs), fw[-1][0])
@@ -197,7 +215,7 @@ def _run_layers(dev, name, T, N, Fin, H, layers, given_state, seed):
     for li in range(layers - 1, -1, -1):
         check(f"c_T[{li}]", states[li].c, fw[li][1][-1])
         check(f"h_T[{li}]", states[li].h, fw[li][0][-1])
-        d, dc0, dh0, dWx, dWh, db = FR.layer_backward(d, GC[li], fw[li][2], P[li], U64)
+        d, dc0, dh0, dWx, dWh, db = FR.layer_backward(d, GC[li], fw[li][2], P[li], U64, gates)
         check(f"dWx[{li}]", cells[li].Wx.grad, dWx)
         check(f"dWh[{li}]", cells[li].Wh.grad, dWh)
         check(f"db[{li}]", cells[li].b.grad, db)
