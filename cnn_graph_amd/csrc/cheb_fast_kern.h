@@ -264,6 +264,78 @@ struct Fwd {
     }
   }
 
+  // The same contraction for the instantiation with registers to spare
+  // (Fin = 1, Fout <= 32: config B; the others sit at the 128-VGPR cap of a
+  // 1024-thread workgroup and spill with the four more registers this takes).
+  // Running byte offsets: pairs are contracted in order s = 0, 1, ..., so the
+  // offsets of order kk = 2s + h advance by two orders per call instead of
+  // being multiplied out.
+  static constexpr bool kPairSeq = FV == 1 && NT == 1;
+  int pw[NT];   // into s_W: W[kk][min(32q + li, Fout - 1)]
+  uint32_t pb;  // of basis[kk][vertex 32 wave + li]: into gB (orders) or s_B (rows)
+  __device__ __forceinline__ void pair_seq_begin() {
+#pragma unroll
+    for (int q = 0; q < NT; ++q) pw[q] = (h * Fout + imin(q * 32 + li, Fout - 1)) * 4;
+    const int m = wave * 32 + li;
+    pb = uint32_t(OB ? h * bord + m : m * FinK + h) * 4u;
+  }
+
+  // pair() of the next pair in order.  S3 = s mod 3 (the ring slot of order kk
+  // is kk % 3 = (2 S3 + h) % 3: a select of two constants); LAST = the final,
+  // possibly half-empty pair (every earlier pair is full: it precedes step
+  // 2s + 2 < K).  All LDS reads of one fin -- the W row and both tiles' ring
+  // words -- are issued together ahead of the first MFMA, so the pair waits
+  // for LDS once, not once per tile and once for W (measured -1.3 us on
+  // config B's forward, profiles/r07_pair); the MFMAs run in pair()'s order
+  // (fin, tile, q), so every accumulator sees the same sequence of operations.
+  template <int S3, bool LAST>
+  __device__ __forceinline__ void pair_seq() {
+    constexpr int SO0 = ((2 * S3) % 3) * 4 * FV, SO1 = ((2 * S3 + 1) % 3) * 4 * FV;
+    const int soff = h ? SO1 : SO0;
+    const bool kv = !LAST || ((K - 1) & ~1) + h < K;
+    const char* wb = reinterpret_cast<const char*>(s_W);
+    const int fstep_w = K * Fout * 4;                           // one fin further in W
+    const uint32_t fstep_b = uint32_t(OB ? K * bord : K) * 4u;  // ... in the basis
+    const uint32_t tstep_b = uint32_t(OB ? kW * 32 : kW * 32 * FinK) * 4u;  // tile 1's vertices
+#pragma unroll
+    for (int fin = 0; fin < FV; ++fin) {
+      float b[NT], a[MT];
+#pragma unroll
+      for (int q = 0; q < NT; ++q) {
+        float w = 0.f;
+        if (kv) w = lds_f(wb + pw[q] + fin * fstep_w);
+        b[q] = q * 32 + li < Fout ? w : 0.f;
+      }
+#pragma unroll
+      for (int t = 0; t < MT; ++t) {  // (tile clamped in mb[]: a valid record either way)
+        const float v = lds_f(ring + mb[t] + soff + fin * 4);
+        a[t] = kv ? v : 0.f;
+      }
+#pragma unroll
+      for (int t = 0; t < MT; ++t) {
+        const int tile = wave + t * kW;
+        if (tile < ntiles) {
+          if (kv && keep_basis) {
+            // (a 32-bit offset from a workgroup-uniform base: no 64-bit address arithmetic)
+            char* base = reinterpret_cast<char*>(OB ? gB : s_B);
+            float* dst = reinterpret_cast<float*>(base + (pb + fin * fstep_b + t * tstep_b));
+            if (OB) *dst = a[t];  // rows >= M: the zero record
+            else if (tile * 32 + li < M) *dst = a[t];
+          }
+          if (!CG_DBG(A.dbg, 4)) {
+#pragma unroll
+            for (int q = 0; q < NT; ++q) acc[t][q] = mfma32(a[t], b[q], acc[t][q]);
+          }
+        }
+      }
+    }
+    if (!LAST) {
+#pragma unroll
+      for (int q = 0; q < NT; ++q) pw[q] += 2 * Fout * 4;
+      pb += uint32_t(OB ? 2 * bord : 2) * 4u;
+    }
+  }
+
   template <int L, int CUR, int PRV, int PRV2>
   __device__ __forceinline__ void step(int k) {
 #pragma clang fp contract(off)
@@ -342,6 +414,24 @@ struct Fwd {
 
   template <int L>
   __device__ __forceinline__ void run() {
+    if constexpr (kPairSeq) {
+      pair_seq_begin();
+      // pair s sits ahead of step 2s + 2; unrolled by 6, s mod 3 is fixed at each site
+      for (int k = 1; k < K; k += 6) {  // k = 1 (mod 6): slots cur/prv/prv2 = 1/0/2
+        step<L, 1, 0, 2>(k);
+        if (k + 1 < K) { pair_seq<0, false>(); step<L, 2, 1, 0>(k + 1); }
+        if (k + 2 < K) step<L, 0, 2, 1>(k + 2);
+        if (k + 3 < K) { pair_seq<1, false>(); step<L, 1, 0, 2>(k + 3); }
+        if (k + 4 < K) step<L, 2, 1, 0>(k + 4);
+        if (k + 5 < K) { pair_seq<2, false>(); step<L, 0, 2, 1>(k + 5); }
+      }
+      switch (((K - 1) >> 1) % 3) {  // the last (possibly half-empty) pair
+        case 0: pair_seq<0, true>(); break;
+        case 1: pair_seq<1, true>(); break;
+        default: pair_seq<2, true>(); break;
+      }
+      return;
+    }
     for (int k = 1; k < K; k += 6) {  // k = 1 (mod 6): slots cur/prv/prv2 = 1/0/2
       step<L, 1, 0, 2>(k);
       if (k + 1 < K) { pair((k - 1) >> 1); step<L, 2, 1, 0>(k + 1); }
