@@ -112,6 +112,12 @@ _SIGNATURES = {
     "cg_flstm_workspace_bytes": ([_c_i32, _c_i32, _c_i32, ctypes.POINTER(_c_sz)], _c_int),
     "cg_flstm_step": ([_c_i32, _c_i32, _c_i32, _c_i32, _vp, _c_sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                        _vp, _vp, _vp, _c_sz, _vp], _c_int),
+    "cg_fres_workspace_bytes": ([_c_i32, _c_i32, _c_i32, _c_i32, ctypes.POINTER(_c_sz),
+                                 ctypes.POINTER(_c_sz)], _c_int),
+    "cg_fres_forward": ([_c_i32, _c_i32, _c_i32, _c_i32, _vp, _c_sz, _vp, _vp, _vp, _c_i32, _vp, _vp,
+                         _vp, _c_sz, _vp], _c_int),
+    "cg_fres_backward": ([_c_i32, _c_i32, _c_i32, _c_i32, _vp, _c_sz, _vp, _vp, _vp, _vp, _c_i32,
+                          _vp, _vp, _c_i32, _vp, _vp, _c_sz, _vp], _c_int),
     "cg_lstm_cell_forward": ([_c_i64, _c_i32, _c_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
                              _c_int),
     "cg_lstm_cell_backward": ([_c_i64, _c_i32, _c_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],

@@ -479,6 +479,19 @@ struct GftGate {
 // out, the gate update instead.
 hipError_t launch_gft(const void* basis, int inverse, int N, int M, int C, const float* in,
                       float* out, bool x3, const GftGate* g, hipStream_t s);
+// The residual block's modes of the same kernel (cg_fres_*).  Analysis of a
+// ReLU backward: the operand is staged as in * [mask_y > 0] (exactly 0 where
+// mask_y == 0) and dz keeps it.  Synthesis: out = act(acc + residual), or
+// out += acc.  Every pointer is read / written at in's and out's own addresses.
+struct GftEx {
+  const float* mask_y;    // NULL = no mask
+  float* dz;              // NULL = the staged operand is not kept
+  const float* residual;  // NULL = 0
+  int relu;
+  int accumulate;
+};
+hipError_t launch_gft_ex(const void* basis, int inverse, int N, int M, int C, const float* in,
+                         float* out, bool x3, const GftEx& e, hipStream_t s);
 // per-frequency contraction (forms of cg_fourier_mix)
 hipError_t launch_fmix(int form, int64_t R, int M, int Cin, int Cout, const float* W, const float* x,
                        const float* g, const float* add, float* out, hipStream_t s);

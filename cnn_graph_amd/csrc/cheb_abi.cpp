@@ -1649,6 +1649,80 @@ int cg_flstm_step(int32_t N, int32_t M, int32_t H, int32_t gates, const void* ba
   return ok();
 }
 
+// ---- residual block with the Fourier filter (k_gft's EX modes, k_fmix) -------------
+static int check_fres(const char* what, int32_t N, int32_t M, int32_t Fin, int32_t Fout,
+                      const void* basis, size_t basis_bytes) {
+  if (N < 1 || M < 1 || Fin < 1 || Fout < 1)
+    return fail(CG_ERR_ARG, "%s: bad shape N=%d M=%d Fin=%d Fout=%d", what, N, M, Fin, Fout);
+  int rc = check_gft(what, N, M, Fin > Fout ? Fin : Fout, basis, basis_bytes);
+  if (rc) return rc;
+  if (int64_t(M) * Fin * Fout >= (int64_t(1) << 31))
+    return fail(CG_ERR_ARG, "%s: M*Fin*Fout exceeds 2^31", what);
+  return CG_OK;
+}
+
+int cg_fres_workspace_bytes(int32_t N, int32_t M, int32_t Fin, int32_t Fout, size_t* fwd_bytes,
+                            size_t* bwd_bytes) {
+  if (N < 1 || M < 1 || Fin < 1 || Fout < 1 || !fwd_bytes || !bwd_bytes)
+    return fail(CG_ERR_ARG, "fres_workspace_bytes: bad arguments");
+  const size_t xin = size_t(N) * M * Fin * 4, yout = size_t(N) * M * Fout * 4;
+  *fwd_bytes = al256(yout);               // yhat
+  *bwd_bytes = al256(yout) + al256(xin);  // ghat, dxhat
+  return ok();
+}
+
+int cg_fres_forward(int32_t N, int32_t M, int32_t Fin, int32_t Fout, const void* basis,
+                    size_t basis_bytes, const float* W, const float* x, const float* residual,
+                    int32_t act, float* xhat, float* y, void* workspace, size_t ws_bytes,
+                    void* stream) {
+  int rc = check_fres("fres_forward", N, M, Fin, Fout, basis, basis_bytes);
+  if (rc) return rc;
+  if (!W || !x || !xhat || !y) return fail(CG_ERR_ARG, "fres_forward: null W / x / xhat / y");
+  if (act != CG_ACT_NONE && act != CG_ACT_RELU)
+    return fail(CG_ERR_ARG, "fres_forward: act must be CG_ACT_NONE or CG_ACT_RELU, got %d", act);
+  const size_t need = al256(size_t(N) * M * Fout * 4);
+  if (!workspace || ws_bytes < need)
+    return fail(CG_ERR_ARG, "fres_forward workspace too small: %zu < %zu", ws_bytes, need);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const bool x3 = cg::option(cg::kOptGemmX3) != 0;
+  float* yhat = static_cast<float*>(workspace);
+  CG_HIP(cg::launch_gft(basis, 0, N, M, Fin, x, xhat, x3, nullptr, s));
+  CG_HIP(cg::launch_fmix(0, N, M, Fin, Fout, W, xhat, nullptr, nullptr, yhat, s));
+  const cg::GftEx e{nullptr, nullptr, residual, act == CG_ACT_RELU, 0};
+  CG_HIP(cg::launch_gft_ex(basis, 1, N, M, Fout, yhat, y, x3, e, s));
+  return ok();
+}
+
+int cg_fres_backward(int32_t N, int32_t M, int32_t Fin, int32_t Fout, const void* basis,
+                     size_t basis_bytes, const float* W, const float* xhat, const float* dy,
+                     const float* y, int32_t act, float* dz, float* dx, int32_t dx_accumulate,
+                     float* dW, void* workspace, size_t ws_bytes, void* stream) {
+  int rc = check_fres("fres_backward", N, M, Fin, Fout, basis, basis_bytes);
+  if (rc) return rc;
+  if (!W || !xhat || !dy || !dW) return fail(CG_ERR_ARG, "fres_backward: null W / xhat / dy / dW");
+  if (act != CG_ACT_NONE && act != CG_ACT_RELU)
+    return fail(CG_ERR_ARG, "fres_backward: act must be CG_ACT_NONE or CG_ACT_RELU, got %d", act);
+  if (act == CG_ACT_RELU && !y) return fail(CG_ERR_ARG, "fres_backward: act relu needs y");
+  if (dx_accumulate && !dx) return fail(CG_ERR_ARG, "fres_backward: dx_accumulate needs dx");
+  const size_t yout = al256(size_t(N) * M * Fout * 4), xin = al256(size_t(N) * M * Fin * 4);
+  const size_t need = yout + (dx ? xin : 0);
+  if (!workspace || ws_bytes < need)
+    return fail(CG_ERR_ARG, "fres_backward workspace too small: %zu < %zu", ws_bytes, need);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const bool x3 = cg::option(cg::kOptGemmX3) != 0;
+  float* ghat = static_cast<float*>(workspace);
+  float* dxhat = reinterpret_cast<float*>(static_cast<char*>(workspace) + yout);
+  const cg::GftEx mask{act == CG_ACT_RELU ? y : nullptr, dz, nullptr, 0, 0};
+  CG_HIP(cg::launch_gft_ex(basis, 0, N, M, Fout, dy, ghat, x3, mask, s));
+  CG_HIP(cg::launch_fmix(2, N, M, Fin, Fout, nullptr, xhat, ghat, nullptr, dW, s));
+  if (dx) {
+    CG_HIP(cg::launch_fmix(1, N, M, Fin, Fout, W, nullptr, ghat, nullptr, dxhat, s));
+    const cg::GftEx acc{nullptr, nullptr, nullptr, 0, dx_accumulate != 0};
+    CG_HIP(cg::launch_gft_ex(basis, 1, N, M, Fin, dxhat, dx, x3, acc, s));
+  }
+  return ok();
+}
+
 static int check_lstm(int64_t R, int32_t H, int32_t gates) {
   if (R < 1 || H < 1) return fail(CG_ERR_ARG, "lstm: bad shape R=%lld H=%d", (long long)R, H);
   if (R * int64_t(H) * 4 >= (int64_t(1) << 31))

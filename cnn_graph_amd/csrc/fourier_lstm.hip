@@ -29,6 +29,10 @@
 //              four gates of 32 units of ONE sample, so the block owns every
 //              gate of the (vertex, unit) pairs it finishes; the accumulators
 //              go through LDS to the k_lstm_fwd gate expressions.
+//              EX (the residual block, cg_fres_*): the moving operand is staged
+//              as in * [mask_y > 0] (the ReLU backward, kept in dz by the first
+//              row block of each column tile), and the store is
+//              out = act(acc + residual) or out += acc.
 //   k_fmix     the per-frequency contraction, one wave per (m, 32 x 32 tile)
 //              on v_mfma_f32_32x32x2_f32 with strided operands: forward,
 //              transposed and weight-gradient forms are the same kernel with
@@ -59,6 +63,11 @@ struct GftArgs {
   float* c_out;
   float* h_out;
   float* act;
+  // EX only
+  const float* mask_y;  // staged operand = in * [mask_y > 0]; NULL = in
+  float* dz;            // receives the staged operand; NULL = not kept
+  const float* res;     // out = act(acc + res); NULL = 0
+  int relu, accum;      // accum: out += acc
 };
 
 // element offset of row 0 of column jj of column tile bx (row stride C); false = padding
@@ -76,7 +85,7 @@ __device__ __forceinline__ bool gft_col(const GftArgs& a, int bx, int jj, int64_
   return j < int64_t(a.N) * a.C;
 }
 
-template <bool X3>
+template <bool X3, bool EX>
 __global__ __launch_bounds__(256) void k_gft(GftArgs a) {
 #pragma clang fp contract(off)
   // X3: 2 buffers x 3 terms x 128 columns x 48 B (16 k as bf16 + 16 B of padding:
@@ -101,15 +110,33 @@ __global__ __launch_bounds__(256) void k_gft(GftArgs a) {
       for (int q = 0; q < 16; ++q) acc[r][c][q] = 0.f;
 
   float v[8];
+  [[maybe_unused]] float vy[8];  // EX: mask_y at the addresses of v
   auto ldB = [&](int ks) {
     const int k0 = ks * 16 + sh * 8;
 #pragma unroll
-    for (int q = 0; q < 8; ++q)
-      v[q] = (sval && k0 + q < a.M) ? a.in[soff + int64_t(k0 + q) * a.C] : 0.f;
+    for (int q = 0; q < 8; ++q) {
+      const bool ok = sval && k0 + q < a.M;
+      const int64_t e = soff + int64_t(k0 + q) * a.C;
+      v[q] = ok ? a.in[e] : 0.f;
+      if constexpr (EX) vy[q] = (ok && a.mask_y) ? a.mask_y[e] : 1.f;
+    }
   };
   ldB(0);
   for (int ks = 0; ks < KS; ++ks) {
     const int buf = ks & 1;
+    if constexpr (EX) {
+      // the mask where the loads are consumed, so that they stay in flight during
+      // the MFMAs; every row block stages the whole k range of its column tile,
+      // so the blocks of row 0 alone keep the masked operand
+#pragma unroll
+      for (int q = 0; q < 8; ++q) v[q] = vy[q] > 0.f ? v[q] : 0.f;
+      if (a.dz && blockIdx.y == 0 && sval) {
+        const int k0 = ks * 16 + sh * 8;
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+          if (k0 + q < a.M) a.dz[soff + int64_t(k0 + q) * a.C] = v[q];
+      }
+    }
     if constexpr (X3) {
       bf16x8* L = reinterpret_cast<bf16x8*>(smem) + buf * (3 * 128 * 3);
       const Split3 sp = x3::split3(v);
@@ -162,7 +189,7 @@ __global__ __launch_bounds__(256) void k_gft(GftArgs a) {
     }
   }
 
-  if (!a.gate) {
+  if (EX || !a.gate) {
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
       int64_t off;
@@ -172,7 +199,15 @@ __global__ __launch_bounds__(256) void k_gft(GftArgs a) {
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
           const int row = (rt0 + r) * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
-          if (row < a.M) a.out[off + int64_t(row) * a.C] = acc[r][c][q];
+          if (row >= a.M) continue;
+          const int64_t e = off + int64_t(row) * a.C;
+          float val = acc[r][c][q];
+          if constexpr (EX) {  // residual and out read at the store's own address
+            if (a.res) val = val + a.res[e];
+            if (a.relu) val = val > 0.f ? val : 0.f;
+            if (a.accum) val = a.out[e] + val;
+          }
+          a.out[e] = val;
         }
     }
     return;
@@ -334,8 +369,9 @@ hipError_t launch_gft_prepare(const float* U, int M, void* basis, hipStream_t s)
   return hipGetLastError();
 }
 
-hipError_t launch_gft(const void* basis, int inverse, int N, int M, int C, const float* in,
-                      float* out, bool x3, const GftGate* g, hipStream_t s) {
+static hipError_t launch_gft_any(const void* basis, int inverse, int N, int M, int C, const float* in,
+                                 float* out, bool x3, const GftGate* g, const GftEx* e,
+                                 hipStream_t s) {
   GftArgs a{};
   const size_t Mp = size_t(gft_pad(M));
   const char* b = static_cast<const char*>(basis);
@@ -353,11 +389,29 @@ hipError_t launch_gft(const void* basis, int inverse, int N, int M, int C, const
   }
   if (ctiles > 2147483647) return hipErrorInvalidValue;
   const dim3 grid(unsigned(ctiles), unsigned(Mp / kGftTile));
-  if (x3)
-    hipLaunchKernelGGL(k_gft<true>, grid, dim3(256), 0, s, a);
-  else
-    hipLaunchKernelGGL(k_gft<false>, grid, dim3(256), 0, s, a);
+  if (e) {
+    a.mask_y = e->mask_y, a.dz = e->dz, a.res = e->residual;
+    a.relu = e->relu, a.accum = e->accumulate;
+    if (x3)
+      hipLaunchKernelGGL((k_gft<true, true>), grid, dim3(256), 0, s, a);
+    else
+      hipLaunchKernelGGL((k_gft<false, true>), grid, dim3(256), 0, s, a);
+  } else if (x3) {
+    hipLaunchKernelGGL((k_gft<true, false>), grid, dim3(256), 0, s, a);
+  } else {
+    hipLaunchKernelGGL((k_gft<false, false>), grid, dim3(256), 0, s, a);
+  }
   return hipGetLastError();
+}
+
+hipError_t launch_gft(const void* basis, int inverse, int N, int M, int C, const float* in,
+                      float* out, bool x3, const GftGate* g, hipStream_t s) {
+  return launch_gft_any(basis, inverse, N, M, C, in, out, x3, g, nullptr, s);
+}
+
+hipError_t launch_gft_ex(const void* basis, int inverse, int N, int M, int C, const float* in,
+                         float* out, bool x3, const GftEx& e, hipStream_t s) {
+  return launch_gft_any(basis, inverse, N, M, C, in, out, x3, nullptr, &e, s);
 }
 
 hipError_t launch_fmix(int form, int64_t R, int M, int Cin, int Cout, const float* W, const float* x,

@@ -48,8 +48,13 @@ class GraphConv:
     """
 
     def __init__(self, filter="chebyshev5", brelu="b1relu", pool="mpool1", device=None,
-                 seed=2017, path="auto"):
+                 seed=2017, path="auto", fourier_fused=False):
+        """fourier_fused: with filter='fourier', run the filter on the MFMA
+        transforms of ops.fourier_conv_act (and, with brelu='b1relu', the
+        residual add and the ReLU in the synthesis' store) instead of
+        ops.fourier_conv; the same weights and results to fp32 rounding."""
         self.device = torch.device(device if device is not None else "cuda")
+        self.fourier_fused = bool(fourier_fused)
         self.filter = getattr(self, filter)
         self.brelu = getattr(self, brelu)
         self.pool = getattr(self, pool)
@@ -116,6 +121,8 @@ class GraphConv:
         N, M, Fin = (int(s) for s in x.shape)
         U = self._fourier_basis(L, x.device)
         W = self._weight_variable([M, Fout, Fin], regularization=False)
+        if self.fourier_fused:  # the transforms of the Fourier gconv-LSTM, no transposes
+            return ops.fourier_conv_act(x, W, self._fourier_prepared(L, x.device))
         return ops.fourier_conv(x, W, U)
 
     def _fourier_basis(self, L, device):
@@ -126,13 +133,29 @@ class GraphConv:
             self._fourier_cache[id(L)] = hit
         return hit[1]
 
+    def _fourier_prepared(self, L, device):
+        """ops.gft_prepare of the cached U, kept next to it."""
+        U = self._fourier_basis(L, device)
+        hit = self._fourier_cache[id(L)]
+        if len(hit) < 3:
+            hit = hit + (ops.gft_prepare(U),)
+            self._fourier_cache[id(L)] = hit
+        return hit[2]
+
     def _filter_act(self, x, L, Fout, K, residual=None):
         """brelu(filter(x) [+ residual]) -- fused into the filter's y store when
         the bound filter / activation are chebyshev5 (or chebyshev2) / b1relu
         (the residual block's `x = filter(x)`, `x = x + x_identity`,
-        `x = brelu(x)`, lib/graph_conv.py:256-262); otherwise separate calls."""
-        fuse = (getattr(self.filter, "__func__", None) in (GraphConv.chebyshev5, GraphConv.chebyshev2)
-                and getattr(self.brelu, "__func__", None) is GraphConv.b1relu)
+        `x = brelu(x)`, lib/graph_conv.py:256-262), or fourier / b1relu with
+        ``fourier_fused`` (the synthesis' store); otherwise separate calls."""
+        filt = getattr(self.filter, "__func__", None)
+        b1relu = getattr(self.brelu, "__func__", None) is GraphConv.b1relu
+        fuse = filt in (GraphConv.chebyshev5, GraphConv.chebyshev2) and b1relu
+        if self.fourier_fused and filt is GraphConv.fourier and b1relu:
+            M, Fin = int(x.shape[1]), int(x.shape[2])
+            W = self._weight_variable([M, Fout, Fin], regularization=False)
+            return ops.fourier_conv_act(x, W, self._fourier_prepared(L, x.device),
+                                        residual=residual, act="relu")
         if not fuse:
             y = self.filter(x, L, Fout, K)
             if residual is not None:

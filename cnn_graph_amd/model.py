@@ -31,6 +31,13 @@ Weights: ``truncated_normal(0, 0.1)`` per ``tf.get_variable('weights')``
 :171): the input's channel groups (``x[..., 0:12]`` and ``x[..., 12:16]``) run
 through separate residual networks, merged as ``X = sum_i relu(net_i) * w_i``
 with ``w_i [M, 2]`` -- same flat-buffer schedule, one Adam, one all-reduce.
+
+``filter="fourier"`` (``params['filter'] = 'fourier'``, the configuration of the
+reference's published humanflow-ln-period runs; lib/graph_conv.py:83-111) runs
+the same schedule with every filter on the MFMA transforms (cg_fres_forward /
+cg_fres_backward): weights ``[M, Fout, Fin]``, the saved tensor of a filter is
+its spectrum xhat, U = ``graph.fourier(L)`` prepared once; ``K`` is accepted
+and ignored as at lib/graph_conv.py:103, and no Chebyshev plan is built.
 """
 from __future__ import annotations
 
@@ -40,6 +47,7 @@ import math
 import torch
 
 from . import _lib
+from . import filter as _filter
 from . import ops
 from .graph_conv import truncated_normal_
 from .plan import plan_for
@@ -138,17 +146,92 @@ class _ResNet:
         self._b(0, dh, bufs[(cur + 1) % 3], None, False, s)  # conv_init (no dx: x is data)
 
 
+class _FourierResNet(_ResNet):
+    """The same network with the Fourier filter: _ResNet's forward / backward
+    schedule over cg_fres_forward / cg_fres_backward.  Weights [M, Fout, Fin]
+    (lib/graph_conv.py:105); the forward saves each filter's spectrum xhat."""
+
+    def __init__(self, owner, scope: str, Fin: int, off: int, gen):
+        self.o = owner
+        N, M, F = owner.N, owner.M, owner.nfilter
+        layers = [(f"{scope}conv_init/weights", Fin, F, "relu")]
+        for i in range(owner.R):
+            layers.append((f"{scope}residual_layer_{i}/sublayer0/weights", F, F, "relu"))
+            layers.append((f"{scope}residual_layer_{i}/sublayer1/weights", F, F, "relu"))
+        layers.append((f"{scope}convN/weights", F, owner.Fout_last, "none"))
+        self.layers = layers
+        self.Fin = Fin
+        f32 = dict(device=owner.device, dtype=torch.float32)
+        self.W, self.dW = [], []
+        for _, fi, fo, _ in layers:
+            sz = M * fo * fi
+            w = owner.flat[off:off + sz].view(M, fo, fi)
+            truncated_normal_(w, 0.1, gen)
+            self.W.append(w)
+            self.dW.append(owner.grad[off:off + sz].view(M, fo, fi))
+            off += sz
+        self.end = off
+        self.names = [name for name, *_ in layers]
+        self.xhat = [torch.empty((N, M, fi), **f32) for _, fi, _, _ in layers]
+        self.out = [torch.empty((N, M, fo), **f32) for _, _, fo, _ in layers]
+        self.g = [torch.empty((N, M, F), **f32) for _ in range(3)]
+
+    @staticmethod
+    def sizes(Fin, F, M, R, Fout_last):
+        return [M * F * Fin] + [M * F * F] * (2 * R) + [M * Fout_last * F]
+
+    def ws_bytes(self):
+        o = self.o
+        return max(max(ops.fres_workspace_bytes(o.N, o.M, fi, fo)) for _, fi, fo, _ in self.layers)
+
+    def _f(self, li, x, res, s):
+        o = self.o
+        _, fi, fo, act = self.layers[li]
+        st = o._fwd(o.N, o.M, fi, fo, o.gft.data_ptr(), o.gft.numel(), self.W[li].data_ptr(),
+                    x.data_ptr(), res.data_ptr() if res is not None else None, ops.ACTS[act],
+                    self.xhat[li].data_ptr(), self.out[li].data_ptr(), o.ws.data_ptr(), o.ws_n, s)
+        _lib.check("cg_fres_forward", st)
+        return self.out[li]
+
+    def _b(self, li, dy, dz, dx, dx_acc, s):
+        o = self.o
+        _, fi, fo, act = self.layers[li]
+        st = o._bwd(o.N, o.M, fi, fo, o.gft.data_ptr(), o.gft.numel(), self.W[li].data_ptr(),
+                    self.xhat[li].data_ptr(), dy.data_ptr(), self.out[li].data_ptr(), ops.ACTS[act],
+                    dz.data_ptr() if dz is not None else None,
+                    dx.data_ptr() if dx is not None else None, int(dx_acc),
+                    self.dW[li].data_ptr(), o.ws.data_ptr(), o.ws_n, s)
+        _lib.check("cg_fres_backward", st)
+
+
+FILTERS = ("chebyshev5", "fourier")
+
+
+def _net_sizes(filter, Fin, F, K, M, R, Fout_last):
+    """Parameter counts of one residual network's filters, in creation order."""
+    if filter == "fourier":
+        return _FourierResNet.sizes(Fin, F, M, R, Fout_last)
+    return _ResNet.sizes(Fin, F, K, R, Fout_last)
+
+
 class _Trainer:
     """Shared pieces of the explicit training schedules: flat parameter /
     gradient / Adam buffers, the MSE loss with its moving average, the
     exchange and the one Adam launch (lib/graph_model.py:246-310)."""
 
     def _setup(self, L, N, nfilter, K, nres_layer_count, Fout_last, learning_rate, decay_rate,
-               decay_steps, device, comm, lmax, total):
+               decay_steps, device, comm, lmax, total, filter="chebyshev5"):
         self.device = torch.device(device if device is not None else "cuda")
         dev_index = self.device.index if self.device.index is not None else 0
-        self.plan = plan_for(L, lmax=lmax, device=dev_index)
-        self.M = self.plan.M
+        self.filter = filter
+        if filter == "fourier":  # no Chebyshev plan: U, prepared once for the transforms
+            self.plan = None
+            self.M = int(L.shape[0])
+            self.U = _filter.fourier_basis(L, self.device)
+            self.gft = ops.gft_prepare(self.U)
+        else:
+            self.plan = plan_for(L, lmax=lmax, device=dev_index)
+            self.M = self.plan.M
         self.N, self.nfilter, self.K = int(N), int(nfilter), int(K)
         self.R, self.Fout_last = int(nres_layer_count), int(Fout_last)
         self.lr, self.decay_rate, self.decay_steps = learning_rate, decay_rate, decay_steps
@@ -171,6 +254,9 @@ class _Trainer:
         self._fwd, self._bwd, self._mse, self._adam = (h.cg_cheb_forward_layout,
                                                        h.cg_cheb_backward_layout,
                                                        h.cg_mse_loss_ema, h.cg_adam_update)
+        if filter == "fourier":
+            self._fwd, self._bwd = h.cg_fres_forward, h.cg_fres_backward
+        self._net = _FourierResNet if filter == "fourier" else _ResNet
 
     def _alloc_ws(self, nets):
         # one workspace serves every forward and backward call (stream order:
@@ -227,17 +313,21 @@ class ResGNN(_Trainer):
     def __init__(self, L, N: int, Fin: int, nfilter: int, K: int, nres_layer_count: int,
                  Fout_last: int = 2, learning_rate: float = 1e-3, decay_rate: float = 0.95,
                  decay_steps: int | None = None, device=None, seed: int = 2017, comm=None,
-                 lmax: float = 2):
-        total = sum(_ResNet.sizes(Fin, nfilter, K, nres_layer_count, Fout_last))
+                 lmax: float = 2, filter: str = "chebyshev5"):
+        """filter: "chebyshev5" or "fourier" (K is then ignored, lib/graph_conv.py:103)."""
+        if filter not in FILTERS:
+            raise ValueError(f"filter must be one of {FILTERS}, got {filter!r}")
+        total = sum(_net_sizes(filter, Fin, nfilter, K, L.shape[0], nres_layer_count, Fout_last))
         self._setup(L, N, nfilter, K, nres_layer_count, Fout_last, learning_rate, decay_rate,
-                    decay_steps, device, comm, lmax, total)
+                    decay_steps, device, comm, lmax, total, filter)
         self.Fin = int(Fin)
         gen = torch.Generator(device=self.device)
         gen.manual_seed(seed)
-        self.net = _ResNet(self, "", self.Fin, 0, gen)
+        self.net = self._net(self, "", self.Fin, 0, gen)
         self.layers, self.names = self.net.layers, self.net.names
         self.W, self.dW = self.net.W, self.net.dW
-        self.basis, self.out = self.net.basis, self.net.out
+        # the forward's saved tensors: the Chebyshev bases, or the spectra xhat
+        self.basis, self.out = getattr(self.net, "basis", None), self.net.out
         self._alloc_ws([self.net])
 
     def forward(self, x, stream=None):
@@ -270,16 +360,19 @@ class StackedResGNN(_Trainer):
     def __init__(self, L, N: int, C: int, nfilter: int, K: int, nres_layer_count: int,
                  groups=((0, 12), (12, 16)), Fout_last: int = 2, learning_rate: float = 1e-3,
                  decay_rate: float = 0.95, decay_steps: int | None = None, device=None,
-                 seed: int = 2017, comm=None, lmax: float = 2):
+                 seed: int = 2017, comm=None, lmax: float = 2, filter: str = "chebyshev5"):
+        """filter: "chebyshev5" or "fourier" (K is then ignored, lib/graph_conv.py:103)."""
+        if filter not in FILTERS:
+            raise ValueError(f"filter must be one of {FILTERS}, got {filter!r}")
         groups = [(int(a), int(b)) for a, b in groups]
         if len(groups) < 1 or any(not (0 <= a < b <= C) for a, b in groups):
             raise ValueError(f"bad channel groups {groups} for C={C}")
         self.C, self.groups = int(C), groups
         M = L.shape[0]
-        sizes = [sum(_ResNet.sizes(b - a, nfilter, K, nres_layer_count, Fout_last)) + M * Fout_last
-                 for a, b in groups]
+        sizes = [sum(_net_sizes(filter, b - a, nfilter, K, M, nres_layer_count, Fout_last))
+                 + M * Fout_last for a, b in groups]
         self._setup(L, N, nfilter, K, nres_layer_count, Fout_last, learning_rate, decay_rate,
-                    decay_steps, device, comm, lmax, sum(sizes))
+                    decay_steps, device, comm, lmax, sum(sizes), filter)
         gen = torch.Generator(device=self.device)
         gen.manual_seed(seed)
         f32 = dict(device=self.device, dtype=torch.float32)
@@ -287,7 +380,7 @@ class StackedResGNN(_Trainer):
         self.W, self.dW, self.names = [], [], []
         off = 0
         for i, (a, b) in enumerate(groups):
-            net = _ResNet(self, f"final_merge/VC_{i}/", b - a, off, gen)
+            net = self._net(self, f"final_merge/VC_{i}/", b - a, off, gen)
             off = net.end
             mf = self.M * self.Fout_last
             w = self.flat[off:off + mf].view(self.M, self.Fout_last)

@@ -9,6 +9,8 @@ or a missing library raises.
   bias_act                      -- b1relu / b1tanh / b2relu, lib/graph_conv.py:178-199
   matmul                        -- tf.matmul of fc, lib/graph_conv.py:220-226 (MFMA GEMM)
   fourier_conv                  -- filter_in_fourier, lib/graph_conv.py:83-111
+  fourier_conv_act              -- the same filter inside the residual block (:234-262):
+                                   residual add and ReLU in the synthesis' store
   mpool1, apool1                -- lib/graph_conv.py:201-218
   perm_data                     -- lib/coarsening.py:219-240 (device gather)
   adam_update                   -- lib/graph_model.py:293-298
@@ -1106,6 +1108,109 @@ def fourier_mix(form: str, W=None, x=None, g=None, add=None, out=None):
     _lib.call("cg_fourier_mix", f, R, M, Cin, Cout, _p(W), _p(x) if f != 1 else None,
               _p(g) if f != 0 else None, _p(add), _p(out), _stream(ref))
     return out
+
+
+# -- residual block with the Fourier filter (lib/graph_conv.py:83-111 in :234-262) ------
+def fres_workspace_bytes(N: int, M: int, Fin: int, Fout: int):
+    """(forward, backward) workspace bytes of cg_fres_forward / cg_fres_backward."""
+    fb, bb = ctypes.c_size_t(), ctypes.c_size_t()
+    _lib.call("cg_fres_workspace_bytes", int(N), int(M), int(Fin), int(Fout), ctypes.byref(fb),
+              ctypes.byref(bb))
+    return fb.value, bb.value
+
+
+def fres_forward(basis, W, x, residual=None, act: str = "none", out_xhat=None, out_y=None):
+    """y = act(U (W[m] U^T x) + residual) in three launches (cg_fres_forward):
+    x [N, M, Fin], W [M, Fout, Fin], basis from gft_prepare.  Returns
+    (xhat [N, M, Fin], y [N, M, Fout])."""
+    for name, t in (("x", x), ("W", W)):
+        _check_dev(name, t)
+    x, W = x.contiguous(), W.contiguous()
+    N, M, Fin = (int(s) for s in x.shape)
+    if W.dim() != 3 or tuple(W.shape[::2]) != (M, Fin):
+        raise ValueError(f"W must be [M, Fout, Fin] = [{M}, *, {Fin}], got {tuple(W.shape)}")
+    Fout = int(W.shape[1])
+    f32 = dict(device=x.device, dtype=torch.float32)
+    if residual is not None:
+        _check_dev("residual", residual)
+        residual = residual.contiguous()
+        if residual.numel() != N * M * Fout:
+            raise ValueError(f"residual must be [N, M, Fout] = [{N}, {M}, {Fout}]")
+    xhat = out_xhat if out_xhat is not None else torch.empty((N, M, Fin), **f32)
+    y = out_y if out_y is not None else torch.empty((N, M, Fout), **f32)
+    _check_out("xhat", xhat, (N, M, Fin))
+    _check_out("y", y, (N, M, Fout))
+    fb, _ = fres_workspace_bytes(N, M, Fin, Fout)
+    ws = torch.empty(fb, device=x.device, dtype=torch.uint8)
+    _lib.call("cg_fres_forward", N, M, Fin, Fout, _p(basis), basis.numel(), _p(W), _p(x),
+              _p(residual), ACTS[act], _p(xhat), _p(y), _p(ws), fb, _stream(x))
+    return xhat, y
+
+
+def fres_backward(basis, W, xhat, dy, y=None, act: str = "none", need_dz: bool = True, dx=None,
+                  dx_accumulate: bool = False, need_dx: bool = True, out_dz=None, out_dW=None):
+    """Backward through fres_forward (cg_fres_backward): returns (dx, dW, dz)
+    with dz = dy * [y > 0] the gradient of the residual input; with
+    dx_accumulate the input gradient is added into the given ``dx``."""
+    for name, t in (("W", W), ("xhat", xhat), ("dy", dy)):
+        _check_dev(name, t)
+    dy, W = dy.contiguous(), W.contiguous()
+    N, M, Fout = (int(s) for s in dy.shape)
+    Fin = int(W.shape[2])
+    f32 = dict(device=dy.device, dtype=torch.float32)
+    if act == "relu":
+        if y is None:
+            raise ValueError("act relu needs the forward's output y")
+        _check_out("y", y, (N, M, Fout))
+    _check_out("xhat", xhat, (N, M, Fin))
+    if need_dx and dx is None:
+        if dx_accumulate:
+            raise ValueError("dx_accumulate needs a dx tensor")
+        dx = torch.empty((N, M, Fin), **f32)
+    if not need_dx:
+        dx = None
+    if dx is not None:
+        _check_out("dx", dx, (N, M, Fin))
+    dz = None
+    if need_dz:
+        dz = out_dz if out_dz is not None else torch.empty((N, M, Fout), **f32)
+        _check_out("dz", dz, (N, M, Fout))
+    dW = out_dW if out_dW is not None else torch.empty((M, Fout, Fin), **f32)
+    _check_out("dW", dW, (M, Fout, Fin))
+    _, bb = fres_workspace_bytes(N, M, Fin, Fout)
+    ws = torch.empty(bb, device=dy.device, dtype=torch.uint8)
+    _lib.call("cg_fres_backward", N, M, Fin, Fout, _p(basis), basis.numel(), _p(W), _p(xhat), _p(dy),
+              _p(y) if act == "relu" else None, ACTS[act], _p(dz), _p(dx), int(dx_accumulate),
+              _p(dW), _p(ws), bb, _stream(dy))
+    return dx, dW, dz
+
+
+class _FourierAct(torch.autograd.Function):
+    """y = act(fourier(x; W) + residual) over cg_fres_forward / cg_fres_backward;
+    saves xhat and y, the residual's gradient is the masked dz."""
+
+    @staticmethod
+    def forward(ctx, x, W, residual, basis, act: str):
+        xhat, y = fres_forward(basis, W, x, residual, act)
+        ctx.save_for_backward(xhat, W, y, basis)
+        ctx.act, ctx.has_res = act, residual is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        xhat, W, y, basis = ctx.saved_tensors
+        need_dz = ctx.has_res and ctx.needs_input_grad[2]
+        dx, dW, dz = fres_backward(basis, W, xhat, dy, y, ctx.act, need_dz=need_dz,
+                                   need_dx=ctx.needs_input_grad[0])
+        return dx, dW, dz, None, None
+
+
+def fourier_conv_act(x, W, basis, residual=None, act: str = "none"):
+    """act(filter_in_fourier(x; W) + residual) on the MFMA transforms with the
+    residual add and the ReLU in the synthesis' store: x [N, M, Fin], W [M, Fout,
+    Fin], basis = gft_prepare(U), residual [N, M, Fout] or None, act "none" /
+    "relu" -> [N, M, Fout]."""
+    return _FourierAct.apply(x, W, residual, basis, act)
 
 
 def flstm_supported(M: int, H: int, Fin: int) -> bool:

@@ -399,6 +399,44 @@ int cg_flstm_step(int32_t N, int32_t M, int32_t H, int32_t gates, const void* ba
                   float* hhat, void* workspace, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Residual GraphConv block with the Fourier filter (lib/graph_conv.py:83-111
+ * inside :234-262) on the transform kernels above.  Additive to version 301.
+ * The filter math is cg_fourier_forward's; x, y, dy, dx, dz, residual are
+ * [N][M][F] and the spectral tensors keep that sample-major layout (xhat
+ * [N][M][Fin]).  W [M][Fout][Fin]; basis: cg_gft_prepare's buffer.  Any
+ * N, M, Fin, Fout >= 1.
+ *
+ * cg_fres_forward, three launches: xhat = U^T x (an output: the backward's
+ * saved tensor), yhat = W[m] xhat per frequency (workspace), then
+ * y = act(U yhat + residual) in the synthesis' store.  residual may be NULL;
+ * act CG_ACT_NONE or CG_ACT_RELU.
+ *
+ * cg_fres_backward: g = dy * [y > 0] with y the forward's OUTPUT (act RELU;
+ * with CG_ACT_NONE g = dy and y may be NULL), applied while the analysis
+ * stages dy, exactly 0 where y == 0; dz (may be NULL) receives g, the gradient
+ * of the residual input.  ghat = U^T g; dW[m] = sum_n ghat[n][m] (x)
+ * xhat[n][m] (n in increasing order: two runs agree bitwise); dxhat = W[m]^T
+ * ghat; dx = U dxhat, or dx += U dxhat with dx_accumulate != 0 (the semantics
+ * of cg_cheb_backward_ex).  dx NULL skips the last two launches (4 launches,
+ * 2 without dx).  dy, y, dz, dx, xhat and the workspace must not alias.
+ *
+ * workspace: cg_fres_workspace_bytes; the forward's is dead once the call has
+ * executed, so one buffer of max(fwd, bwd) bytes serves both.  Argument errors
+ * (null required pointer, size < 1, short workspace, act RELU without y,
+ * dx_accumulate without dx) return CG_ERR_ARG before any device work.
+ * ------------------------------------------------------------------------- */
+int cg_fres_workspace_bytes(int32_t N, int32_t M, int32_t Fin, int32_t Fout, size_t* fwd_bytes,
+                            size_t* bwd_bytes);
+int cg_fres_forward(int32_t N, int32_t M, int32_t Fin, int32_t Fout, const void* basis,
+                    size_t basis_bytes, const float* W, const float* x, const float* residual,
+                    int32_t act, float* xhat, float* y, void* workspace, size_t ws_bytes,
+                    void* stream);
+int cg_fres_backward(int32_t N, int32_t M, int32_t Fin, int32_t Fout, const void* basis,
+                     size_t basis_bytes, const float* W, const float* xhat, const float* dy,
+                     const float* y, int32_t act, float* dz, float* dx, int32_t dx_accumulate,
+                     float* dW, void* workspace, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
  * gconv-LSTM cell pointwise part (lib/gconv_lstm.py:77-221, GConvLSTMCell).
  * The cell's eight cheby_conv calls are two chebyshev5 calls with the four
  * gate weights concatenated: gx = cheb(x; [Wzxt|Wixt|Wfxt|Woxt]) and

@@ -8,6 +8,9 @@
   E   gconv-LSTM layer on grid(32) 8-NN:    T=12, N=128, Fin=2, H=32, K=3 (fwd+bwd, BPTT)
   EF  the same layer with the Fourier filter (filter_type="fourier_conv"): hconv="fused"
       against hconv="unfused", the h-step's launches and the transforms' share of peak
+  RF  the ResGNN training step with the Fourier filter at the reference's published shape
+      (M=1024, batch 100, 10 channels, nfilter 32, 4 residual layers) against forward +
+      backward of the same network on the older unfused ops under autograd
 
 fwd / bwd are HIP-event timings (torch's current stream, where every C-ABI
 call is enqueued) of one chebyshev5 forward and backward (dx + dW), median of
@@ -15,7 +18,7 @@ rounds; alg_GBps uses SURVEY.md §8d's algorithmic bytes.  Each line carries a
 `cpu_baseline`: the oracle's fwd+bwd of the same config on the host cores
 (bench.py's CPU legs -- the only place outside tests/ that runs oracle/),
 median of the timed passes, with the sub-batch and pass count stated.
-Usage: python scripts/bench_configs.py [A C1 C2 D E R] [--d-batch N] [--layout auto|rows|planes]
+Usage: python scripts/bench_configs.py [A C1 C2 D E EF R RF] [--d-batch N] [--layout auto|rows|planes]
                                        [--no-cpu] [--cpu-seconds S]
 """
 from __future__ import annotations
@@ -242,6 +245,110 @@ def resgnn_config(dev, N=100, Fin=2, nfilter=32, K=20, nres=4):
             "step_ms": round(ms, 3), "samples_per_s": round(N / (ms * 1e-3), 1)}
 
 
+PUBLISHED_RF_MS = 222.8  # nips2016/humanflow-ln-period.ipynb: 22.28 s per 100 steps
+
+
+def resgnn_fourier_config(dev, N=100, Fin=10, nfilter=32, nres=4, samples=8):
+    """RF: the reference's published ResGNN runs (params['filter'] = 'fourier',
+    M = 1024, batch 100, 10 input channels, nfilter 32, 4 residual layers,
+    Fout_last 2) on config R's graph recipe.  The training step of
+    ResGNN(filter="fourier") and, interleaved in the same process, forward +
+    backward of the same network composed from the older unfused ops
+    (GraphConv(filter="fourier") under autograd: no loss kernel, no Adam), one
+    event pair per pass; plus the transform launches at the hidden-layer shape."""
+    from cnn_graph_amd import _lib
+    from cnn_graph_amd.graph_conv import GraphConv
+    from cnn_graph_amd.model import ResGNN
+    _, L = graph_e()
+    M = L.shape[0]
+    model = ResGNN(L, N=N, Fin=Fin, nfilter=nfilter, K=20, nres_layer_count=nres, device=dev,
+                   filter="fourier")
+    g = torch.Generator(device=dev)
+    g.manual_seed(3)
+    x = torch.rand((N, M, Fin), device=dev, generator=g)
+    labels = torch.rand((N, M, 2), device=dev, generator=g)
+    nets = {}
+    for key, fused in (("unfused", False), ("fused_autograd", True)):
+        gc = GraphConv(filter="fourier", device=dev, fourier_fused=fused)
+        gc.residual_network(x, L, nfilter, 20, nres, Fout_last=2)
+        with torch.no_grad():
+            for name, w in model.parameters().items():
+                gc.weights[name].copy_(w)
+        nets[key] = gc
+
+    def fwdbwd(gc):
+        out = gc.residual_network(x, L, nfilter, 20, nres, Fout_last=2)
+        out.backward(labels)
+        for p in gc.parameters():
+            p.grad = None
+
+    legs = {"step": lambda: model.train_step(x, labels),
+            "unfused": lambda: fwdbwd(nets["unfused"]),
+            "fused_autograd": lambda: fwdbwd(nets["fused_autograd"])}
+
+    def one(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    for fn in legs.values():  # warm every shape of the timed window
+        fn()
+        fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in legs}
+    for _ in range(samples):  # alternate the legs
+        for k, fn in legs.items():
+            ms[k].append(one(fn))
+    stat = {k: [float(np.percentile(v, q)) for q in (50, 10, 90)] for k, v in ms.items()}
+    # the transforms of a hidden filter (C = nfilter), alone
+    f32 = dict(device=dev, dtype=torch.float32)
+    B, F = model.gft, nfilter
+    a, b, c = (torch.randn((N, M, F), generator=g, **f32) for _ in range(3))
+    W = model.W[1]
+    y, xh, dz = (torch.empty((N, M, F), **f32) for _ in range(3))
+    dW = torch.empty_like(W)
+    launches = {
+        "analysis": lambda: ops.gft(B, a, out=xh),
+        "mix": lambda: ops.fourier_mix("fwd", W, x=xh, out=y),
+        "forward_3_launches": lambda: ops.fres_forward(B, W, a, b, "relu", out_xhat=xh, out_y=y),
+        "backward_4_launches": lambda: ops.fres_backward(B, W, xh, c, y, "relu", dx=a, out_dz=dz,
+                                                         out_dW=dW),
+    }
+    lt = {}
+    for name, fn in launches.items():
+        fn()
+        torch.cuda.synchronize()
+        lt[name] = ev_ms(fn, 10)
+    flop = 2.0 * M * M * N * F  # one transform at C = nfilter
+    synth_ms = lt["forward_3_launches"] - lt["analysis"] - lt["mix"]
+    tf = {"analysis": flop / (lt["analysis"] * 1e-3) / 1e12,
+          "synthesis_act_by_difference": flop / (max(synth_ms, 1e-6) * 1e-3) / 1e12}
+    # transform FLOP of a training step: 2 per filter forward, 2 per backward (1 without dx)
+    chans = [(Fin, F)] + [(F, F)] * (2 * nres) + [(F, 2)]
+    step_flop = sum(2.0 * M * M * N * (fi + fo) * 2 for fi, fo in chans) - 2.0 * M * M * N * Fin
+    s, u, fa = stat["step"], stat["unfused"], stat["fused_autograd"]
+    return {"config": "RF", "M": M, "N": N, "Fin": Fin, "nfilter": F, "nres_layer_count": nres,
+            "samples": samples, "gemm_x3": _lib.get_option("gemm_x3"),
+            "filter_calls_per_step": 2 * nres + 2,
+            "step_ms": round(s[0], 3), "step_p10_p90": [round(s[1], 3), round(s[2], 3)],
+            "samples_per_s": round(N / (s[0] * 1e-3), 1),
+            "unfused_fwd_bwd_ms": round(u[0], 3),
+            "unfused_p10_p90": [round(u[1], 3), round(u[2], 3)],
+            "fused_autograd_fwd_bwd_ms": round(fa[0], 3),
+            "fused_autograd_p10_p90": [round(fa[1], 3), round(fa[2], 3)],
+            "ratio_unfused_over_step": round(u[0] / s[0], 3),
+            "published_step_ms_unknown_gpu_one_evaluation_included": PUBLISHED_RF_MS,
+            "launch_ms": {k: round(v, 4) for k, v in lt.items()},
+            "transform_TFLOPs": {k: round(v, 1) for k, v in tf.items()},
+            "transform_frac_x3_roof": {k: round(v * 1e12 / (2.7 * F32_MATRIX_PEAK), 3)
+                                       for k, v in tf.items()},
+            "step_transform_GFLOP": round(step_flop / 1e9, 1),
+            "step_transform_TFLOPs_end_to_end": round(step_flop / (s[0] * 1e-3) / 1e12, 1)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("configs", nargs="*", default=["C1", "C2", "D", "E"])
@@ -304,6 +411,8 @@ def main():
             out = lstm_config(dev, hconv="unfused")
         elif name == "E_step":
             out = lstm_config(dev, hconv="fused")
+        elif name == "RF":
+            out = resgnn_fourier_config(dev)
         elif name == "R":
             out = resgnn_config(dev)
             cpu = lambda: bench.cpu_baseline_resgnn(graph_e()[1], 2, 100, 2, 32, 20, 4,  # noqa: E731
