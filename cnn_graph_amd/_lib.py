@@ -132,6 +132,7 @@ _SIGNATURES = {
     "cg_lstm_seq_status": ([_vp, _c_i32, _vp, ctypes.POINTER(_c_i32), _vp], _c_int),
     "cg_lstm_seq_fault": ([_vp, _c_i32, _c_i32, ctypes.POINTER(_c_i32)], _c_int),
     "cg_plan_set_seq_fault_test": ([_vp, _c_i32], _c_int),
+    "cg_plan_query_stream_dispatch": ([_vp, _c_i32, _c_i32, _c_i32, _c_i32, _c_int, _ip32], _c_int),
     "cg_set_option": ([_c_i32, _c_i32], _c_int),
     "cg_get_option": ([_c_i32, ctypes.POINTER(_c_i32)], _c_int),
     "cg_dropout_forward": ([_vp, ctypes.c_int64, ctypes.c_float, ctypes.c_uint64, _vp, _vp], _c_int),

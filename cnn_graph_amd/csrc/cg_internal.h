@@ -247,6 +247,47 @@ hipError_t launch_fast_backward(const FastGeom& g, int N, const FastBwdArgs& a, 
 // (T_k [N][M][Fin], T_0 = x).  last: also assemble the basis [N*M][Fin*K]
 // from x, slots (T_1..T_{K-2}, N*M*Fin floats apart) and the new T_{K-1}.
 // rperm: row visiting order (NULL = natural).
+// Launch geometry of the sample-major steps (k_cheb_step / k_cheb_last /
+// k_clenshaw_step): a work item is one (sample, row), LPR lanes own its Fin
+// columns (VEC floats per lane), a wave holds 64/LPR rows.
+struct StepGeom {
+  int lpr;      // lanes per row
+  int rpw;      // rows per wave (64 / lpr)
+  int rb;       // row blocks (of 4 waves) per sample
+  int xcd_map;  // 1: sample-per-XCD block mapping
+  int N;        // samples; with xcd_map the grid covers 8 * ceil(N / 8) of
+                // them and the blocks of samples n >= N exit at once
+  unsigned grid;  // blocks to launch
+};
+inline int step_vec(int Fin) { return (Fin % 4 == 0) ? 4 : 1; }  // floats per lane
+inline StepGeom step_geom(int N, int M, int Fin, int vec) {
+  StepGeom g;
+  const int lanes = (Fin + vec - 1) / vec;
+  g.lpr = lanes < 64 ? lanes : 64;
+  g.rpw = 64 / g.lpr;
+  g.rb = (M + 4 * g.rpw - 1) / (4 * g.rpw);
+  // sample-per-XCD mapping keeps each XCD's gathers inside one sample slab in
+  // its own 4 MB L2; slabs larger than that are better shared by all XCDs at
+  // once (all blocks of sample n before sample n+1) so the one slab being
+  // gathered stays in the 256 MB Infinity Cache.  N not a multiple of 8 (the
+  // humanflow ResGNN's batch of 100) pads the grid to 8 * ceil(N / 8) samples
+  // rather than falling back to the sample-major order, which spreads every
+  // sample's blocks over all 8 XCDs (each L2 then holds all N slabs)
+  const int64_t slab = int64_t(M) * Fin * 4;
+  g.xcd_map = (slab <= (int64_t(2) << 20)) ? 1 : 0;
+  g.N = N;
+  const int64_t ns = g.xcd_map ? (int64_t(N) + 7) / 8 * 8 : int64_t(N);
+  g.grid = unsigned(ns * g.rb);
+  return g;
+}
+// LDS bytes of the staged last step (k_cheb_last): past kLdsBytes the last
+// step is k_cheb_step<., true> (per-lane scattered basis stores)
+inline size_t cheb_last_stage_bytes(const StepGeom& g, int Fin, int K) {
+  return size_t(4) * g.rpw * (size_t(Fin) * K + 1) * sizeof(float);
+}
+// The degree-sorted row order serves the sample-major steps from Fin >= 16 on
+// (every row's write is then >= 64 contiguous bytes)
+inline const int* step_rperm(const int* rperm, int Fin) { return (Fin >= 16) ? rperm : nullptr; }
 hipError_t launch_cheb_step(const int* rowptr, const int* col, const float* val, const int* rperm,
                             const float* Tp, const float* Tpp, float* Tout, const float* x,
                             const float* slots, float* basis, int N, int M, int Fin, int K, int k,
@@ -283,11 +324,19 @@ hipError_t launch_vm_to_sm(const float* src, int N, int64_t Q, float* dst, int a
 // D[k*plane + m*Fin*N + fin*N + n] = sum_f dy[n][m][f] W[fin*K+k][f] and per-block
 // dW partials slab[b][FinK][Fout] (wide_dypass_blocks of them; reduce after).
 bool wide_dypass_ok(int FinK, int Fout);
+// FinK <= 8: the VALU kernel k_wide_dypass_small<FinK>, else the MFMA k_wide_dypass
+inline bool wide_dypass_small(int FinK) { return FinK >= 1 && FinK <= 8; }
 int wide_dypass_blocks(int N, int M);
 hipError_t launch_wide_dypass(const float* dy, const float* basis, const float* W, int N, int M,
                               int Fin, int K, int Fout, float* D, int64_t plane, float* slab,
                               hipStream_t s);
 // basis[n][m][fin*K + k] = T[k*plane + m*Fin*N + fin*N + n]
+// rows per tile of k_wide_assemble
+inline int wide_tm(int FinK) {
+  int tm = 8192 / (32 * FinK);  // <= 32 KB of LDS staging, <= 256 items per 8 thread rows
+  if (tm > 32) tm = 32;
+  return tm < 1 ? 1 : tm;
+}
 hipError_t launch_wide_assemble(const float* T, int64_t plane, int N, int M, int Fin, int K,
                                 float* basis, hipStream_t s);
 

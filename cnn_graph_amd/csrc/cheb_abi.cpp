@@ -453,6 +453,55 @@ int workspace_bytes(const cg_plan* p, int32_t N, int32_t Fin, int32_t K, int32_t
   return CG_OK;
 }
 
+// What forward_impl / backward_impl launch on the streaming path, for the test
+// hook cg_plan_query_stream_dispatch: the branches of the two functions in
+// their order, decided by the predicates they call.  Host only, no launch.
+// out: CG_SD_* of include/cheb_mi355_testing.h.
+void stream_dispatch(const cg_plan* p, int32_t N, int32_t Fin, int32_t K, int32_t Fout, int layout,
+                     int32_t* out) {
+  std::fill(out, out + CG_SD_COUNT, 0);
+  const int FinK = Fin * K;
+  const bool wide = stream_ws(p, N, Fin, K, Fout).wide;
+  out[CG_SD_WIDE] = wide;
+  out[CG_SD_LAST_STAGED] = -1;
+  if (wide) {
+    const cg::WideGeom g = cg::wide_geometry(N, Fin, p->M);
+    out[CG_SD_G] = g.G;
+    out[CG_SD_CB] = g.CB;
+    out[CG_SD_PL] = g.pl;
+    if (K >= 2) {  // (K == 1: the basis is a copy of x, no step)
+      const bool fused_last = cg::wide_last_ok(g, Fin, K, p->rperm != nullptr);
+      out[CG_SD_FUSED_LAST] = fused_last;
+      out[CG_SD_ASSEMBLE_TM] = fused_last ? 0 : cg::wide_tm(FinK);
+      out[CG_SD_SORTED_FWD] = p->rperm != nullptr;
+      out[CG_SD_SORTED_BWD] = p->trperm != nullptr;
+    }
+    if (cg::wide_dypass_ok(FinK, Fout)) out[CG_SD_DYPASS] = cg::wide_dypass_small(FinK) ? 1 : 2;
+    return;
+  }
+  const bool group = use_group(p, Fin, K, Fout);
+  const int vec = cg::step_vec(Fin);
+  const cg::StepGeom g = cg::step_geom(N, p->M, Fin, vec);
+  out[CG_SD_VEC] = vec;
+  out[CG_SD_LPR] = g.lpr;
+  out[CG_SD_RPW] = g.rpw;
+  out[CG_SD_XCD_MAP] = g.xcd_map;
+  if (K >= 2) {
+    if (layout == CG_BASIS_PLANES && group) {
+      out[CG_SD_GROUP_FWD] = 1;
+    } else {
+      out[CG_SD_SORTED_FWD] = cg::step_rperm(p->rperm, Fin) != nullptr;
+      if (layout != CG_BASIS_PLANES)  // (planes: every step writes its own plane)
+        out[CG_SD_LAST_STAGED] =
+            cg::cheb_last_stage_bytes(g, Fin, K) <= size_t(cg::kLdsBytes) ? 1 : 0;
+    }
+  }
+  if (group)
+    out[CG_SD_GROUP_BWD] = cg::grp_clen_dy_ok(p->M, p->nnzT, K, Fout) ? 2 : 1;
+  else
+    out[CG_SD_SORTED_BWD] = cg::step_rperm(p->trperm, Fin) != nullptr;
+}
+
 }  // namespace
 
 namespace cg {
@@ -844,7 +893,7 @@ int forward_impl(cg_plan* plan, int32_t N, int32_t Fin, int32_t K, int32_t Fout,
     // planes layout: T_k IS plane k of the basis (plane 0 = x: copied unless
     // the caller placed x there), every step writes its own plane, no assembly
     // step (lib/graph_conv.py:159-169)
-    const int* rperm = (Fin >= 16) ? plan->rperm : nullptr;
+    const int* rperm = cg::step_rperm(plan->rperm, Fin);
     auto P = [&](int k) { return basis + size_t(k) * slot; };
     if (x != basis) CG_HIP(hipMemcpyAsync(basis, x, slot * sizeof(float), hipMemcpyDeviceToDevice, s));
     for (int k = 1; k < K; ++k)
@@ -854,7 +903,7 @@ int forward_impl(cg_plan* plan, int32_t N, int32_t Fin, int32_t K, int32_t Fout,
   } else {
     // sample-major steps: T_0 = x, T_j (1 <= j <= K-2) in slots[j-1], the last
     // step writes the whole basis (lib/graph_conv.py:159-172)
-    const int* rperm = (Fin >= 16) ? plan->rperm : nullptr;
+    const int* rperm = cg::step_rperm(plan->rperm, Fin);
     auto T = [&](int k) -> const float* { return k == 0 ? x : slots + size_t(k - 1) * slot; };
     for (int k = 1; k < K; ++k) {
       const bool last = (k == K - 1);
@@ -1033,7 +1082,7 @@ int backward_impl(cg_plan* plan, int32_t N, int32_t Fin, int32_t K, int32_t Fout
                                    M, Fin, K,
                                    dA, dx, dx_acc, s));
       } else {
-        const int* rperm = (Fin >= 16) ? plan->trperm : nullptr;
+        const int* rperm = cg::step_rperm(plan->trperm, Fin);
         auto G = [&](int k) { return dA + size_t(k) * slot; };
         // G_{K-1} = D_{K-1} already sits in its plane (G lives in place of D):
         // the last order's step would only rewrite it (D's 17 GB at N = 256);
@@ -1929,6 +1978,22 @@ int cg_lstm_seq_status(const cg_plan* plan, int32_t N, const void* workspace, in
 int cg_plan_set_seq_fault_test(cg_plan* plan, int32_t step) {
   if (!plan || step < -1) return fail(CG_ERR_ARG, "plan_set_seq_fault_test: bad arguments");
   plan->seq_fault_test = step;
+  return ok();
+}
+
+int cg_plan_query_stream_dispatch(const cg_plan* plan, int32_t N, int32_t Fin, int32_t K,
+                                  int32_t Fout, int layout, int32_t out[16]) {
+  int rc = check_shape(plan, N, Fin, K, Fout);
+  if (rc) return rc;
+  if (!out) return fail(CG_ERR_ARG, "null dispatch out-pointer");
+  if ((rc = check_layout(plan, Fin, K, Fout, layout))) return rc;
+  int pf = 0, pb = 0;
+  if ((rc = choose_path(plan, Fin, K, Fout, false, &pf))) return rc;
+  if ((rc = choose_path(plan, Fin, K, Fout, true, &pb))) return rc;
+  if (pf != CG_PATH_STREAM || pb != CG_PATH_STREAM)
+    return fail(CG_ERR_UNSUPPORTED, "not on the streaming path: M=%d Fin=%d K=%d Fout=%d", plan->M,
+                Fin, K, Fout);
+  stream_dispatch(plan, N, Fin, K, Fout, layout, out);
   return ok();
 }
 

@@ -48,16 +48,7 @@ inline int grid_for(int64_t total, int block) {
 // its own samples (n = xcd, xcd+8, ...) and that slab stays in its L2.
 // The last step assembles the basis row (n, r) = [fin][k] (lib/graph_conv.py:172)
 // from the own-row T_0..T_{K-2} and the fresh T_{K-1}: every basis byte is
-// written once, by one lane, contiguously.
-struct StepGeom {
-  int lpr;      // lanes per row
-  int rpw;      // rows per wave (64 / lpr)
-  int rb;       // row blocks (of 4 waves) per sample
-  int xcd_map;  // 1: sample-per-XCD block mapping
-  int N;        // samples; with xcd_map the grid covers 8 * ceil(N / 8) of
-                // them and the blocks of samples n >= N exit at once
-  unsigned grid;  // blocks to launch
-};
+// written once, by one lane, contiguously.  (StepGeom / step_geom: cg_internal.h)
 
 // Block -> (sample, row block).  Returns false for the padding blocks of the
 // sample-per-XCD mapping (N not a multiple of 8), which exit immediately.
@@ -572,27 +563,6 @@ __global__ __launch_bounds__(256) void k_clenshaw_step(ClenArgs a, StepGeom g) {
     if (a.dx_acc && a.k == 0) o = V::add(V::ld(a.Gout + rbase + f0), o);
     V::st(a.Gout + rbase + f0, o);
   }
-}
-
-StepGeom step_geom(int N, int M, int Fin, int vec) {
-  StepGeom g;
-  const int lanes = (Fin + vec - 1) / vec;
-  g.lpr = lanes < 64 ? lanes : 64;
-  g.rpw = 64 / g.lpr;
-  g.rb = (M + 4 * g.rpw - 1) / (4 * g.rpw);
-  // sample-per-XCD mapping keeps each XCD's gathers inside one sample slab in
-  // its own 4 MB L2; slabs larger than that are better shared by all XCDs at
-  // once (all blocks of sample n before sample n+1) so the one slab being
-  // gathered stays in the 256 MB Infinity Cache.  N not a multiple of 8 (the
-  // humanflow ResGNN's batch of 100) pads the grid to 8 * ceil(N / 8) samples
-  // rather than falling back to the sample-major order, which spreads every
-  // sample's blocks over all 8 XCDs (each L2 then holds all N slabs)
-  const int64_t slab = int64_t(M) * Fin * 4;
-  g.xcd_map = (slab <= (int64_t(2) << 20)) ? 1 : 0;
-  g.N = N;
-  const int64_t ns = g.xcd_map ? (int64_t(N) + 7) / 8 * 8 : int64_t(N);
-  g.grid = unsigned(ns * g.rb);
-  return g;
 }
 
 // C = op(A) op(B), 64x64 output tile per 256-thread block, each wave a 32x32
@@ -1362,10 +1332,10 @@ hipError_t launch_cheb_step(const int* rowptr, const int* col, const float* val,
                             bool last, hipStream_t s) {
   ChebStepArgs a{rowptr, col, val, rperm, Tp, Tpp, Tout, x, slots,
                  int64_t(N) * M * Fin, basis, M, Fin, K, k};
-  const int vec = (Fin % 4 == 0) ? 4 : 1;
+  const int vec = step_vec(Fin);
   const StepGeom g = step_geom(N, M, Fin, vec);
   const dim3 grid(g.grid), block(256);
-  const size_t stage = size_t(4) * g.rpw * (size_t(Fin) * K + 1) * sizeof(float);
+  const size_t stage = cheb_last_stage_bytes(g, Fin, K);
   // up to the CU's whole LDS: the per-lane scattered basis stores of
   // k_cheb_step<., true> are ~10x slower (config R's 32 x 20 hidden layers:
   // 835 us per call, profiles/r02_resgnn)
@@ -1392,7 +1362,7 @@ hipError_t launch_clenshaw(const int* trowptr, const int* tcol, const float* tva
                            const float* Gn1, const float* Gn2, float* Gout, const float* Dk, int N,
                            int M, int Fin, int K, int k, int dx_acc, hipStream_t s) {
   ClenArgs a{trowptr, tcol, tval, rperm, Gn1, Gn2, Gout, Dk, M, Fin, K, k, dx_acc};
-  const int vec = (Fin % 4 == 0) ? 4 : 1;
+  const int vec = step_vec(Fin);
   const StepGeom g = step_geom(N, M, Fin, vec);
   const dim3 grid(g.grid), block(256);
   if (vec == 4) hipLaunchKernelGGL((k_clenshaw_step<4>), grid, block, 0, s, a, g);

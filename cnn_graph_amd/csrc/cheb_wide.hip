@@ -592,12 +592,6 @@ __global__ __launch_bounds__(256) void k_wide_dypass_small(const float* __restri
   }
 }
 
-inline int wide_tm(int FinK) {
-  int tm = 8192 / (32 * FinK);  // <= 32 KB of LDS staging, <= 256 items per 8 thread rows
-  if (tm > 32) tm = 32;
-  return tm < 1 ? 1 : tm;
-}
-
 }  // namespace
 
 WideGeom wide_geometry(int N, int Fin, int M) {
@@ -704,7 +698,7 @@ hipError_t launch_wide_dypass(const float* dy, const float* basis, const float* 
   if (!wide_dypass_ok(Fin * K, Fout)) return hipErrorInvalidValue;
   if ((reinterpret_cast<uintptr_t>(dy) & 15) != 0) return hipErrorInvalidValue;
   const dim3 grid(wide_dypass_blocks(N, M));
-  switch (Fin * K) {
+  switch (wide_dypass_small(Fin * K) ? Fin * K : 0) {
 #define CG_DP(FJ_)                                                                              \
   case FJ_:                                                                                     \
     hipLaunchKernelGGL(k_wide_dypass_small<FJ_>, grid, dim3(256), 0, s, dy, basis, W, N, M, Fin, K, \

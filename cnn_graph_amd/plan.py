@@ -70,6 +70,21 @@ class ChebPlan:
         hand-off; -1 turns it off."""
         _lib.call("cg_plan_set_seq_fault_test", self._h, int(step))
 
+    # out[] of cg_plan_query_stream_dispatch, in order (CG_SD_* of cheb_mi355_testing.h)
+    STREAM_DISPATCH_FIELDS = ("wide", "G", "CB", "pl", "fused_last", "assemble_tm", "dypass",
+                              "sorted_rows_fwd", "sorted_rows_bwd", "group_fwd", "group_bwd",
+                              "vec", "lpr", "rpw", "xcd_map", "last_staged")
+
+    def stream_dispatch(self, N, Fin, K, Fout, layout: str = "rows") -> dict:
+        """Test hook (cg_plan_query_stream_dispatch): which kernels the streaming
+        forward and backward would launch for this shape, as a dict of
+        STREAM_DISPATCH_FIELDS.  Host only, nothing is launched.  Raises CGError
+        when the shape is not on the streaming path both ways."""
+        out = (ctypes.c_int32 * 16)()
+        _lib.call("cg_plan_query_stream_dispatch", self._h, int(N), int(Fin), int(K), int(Fout),
+                  _lib.BASIS_LAYOUTS[layout], out)
+        return dict(zip(self.STREAM_DISPATCH_FIELDS, (int(v) for v in out)))
+
     # workspaces above this size are not kept by the plan (a config-D backward
     # at N = 256 needs 51.5 GB: holding it for the plan's lifetime would pin it
     # for every later model that shares the plan through plan_for)

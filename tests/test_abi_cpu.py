@@ -19,7 +19,8 @@ def test_library_exports_every_header_symbol(built_lib):
     assert missing == []
     assert set(syms) == set(_lib._SIGNATURES), "ctypes signatures out of sync with the headers"
     # the test-only fault hook is not part of the integration surface
-    assert "cg_plan_set_seq_fault_test" not in public and testing == ["cg_plan_set_seq_fault_test"]
+    assert testing == ["cg_plan_query_stream_dispatch", "cg_plan_set_seq_fault_test"]
+    assert not set(testing) & set(public)
 
 
 def test_version(built_lib):
@@ -85,6 +86,7 @@ def test_options_roundtrip_and_validation(built_lib):
 def test_plan_variant_validation(built_lib):
     h = _lib.lib()
     assert h.cg_plan_set_variant(None, 0) == _lib.CG_ERR_ARG
+    assert h.cg_plan_query_stream_dispatch(None, 1, 1, 1, 1, 0, None) == _lib.CG_ERR_ARG
 
 
 def _i32(a):

@@ -311,6 +311,10 @@ def test_planes_layout_skewed_graph(dev):
         T.append(np.stack([2 * (Lt @ T[-1][n]) for n in range(N)]) - T[-2])
     ref = np.stack(T, axis=-1).reshape(N * M, Fin * K)  # column fin*K + k
     assert O.normwise_err(rr.basis.cpu().numpy(), ref) < 1e-5
+    # and bitwise against the oracle's fp32 CSR-order recurrence (the sorted
+    # row order changes which lane computes a row, not the row's sum)
+    ob, _ = O.cheb_forward(x.cpu().numpy(), Lt.indptr, Lt.indices, Lt.data, W.cpu().numpy(), K)
+    assert np.array_equal(rr.basis.cpu().numpy(), ob), "rows-layout basis not bit-exact"
 
 
 @pytest.mark.parametrize("variant,gname,N,Fin,K,Fout", [("steps", "golden_B.npz", 3, 32, 5, 32),

@@ -80,14 +80,21 @@ def test_config_c_golden(dev, graph_c, prefix):
 
 
 @pytest.mark.parametrize("N,Fin,K,Fout", [(128, 1, 5, 32), (64, 2, 5, 16), (48, 1, 3, 8),
-                                          (32, 1, 4, 40)])
+                                          (16, 1, 3, 8), (32, 1, 4, 40)])
 def test_config_c_wide_vs_narrow_layout(dev, graph_c, N, Fin, K, Fout):
     """Config C layer 1 (Fin < 8) on the wide-column streaming layout
-    (cheb_wide.hip, [M][Fin*N]; B % 128 == 0: 8 XCD column groups, else one;
+    (cheb_wide.hip, [M][Fin*N]; the B = Fin*N columns are cut into the most
+    groups G of 8, 4, 2 with B % (32 G) == 0, else one, and the shape is wide
+    only if the CB = B / G columns of a group make a power of two <= 64 of
+    lanes at 4, 2 or 1 floats per lane -- in practice B a power of two <= 2048;
     Fout % 8 == 0 and <= 32: the fused dy pass, else the row-GEMM planes)
     vs the sample-major layout (variant 'narrow'): both vs the oracle incl.
     the dx accumulation of the residual block's backward; the forward
-    (basis, y) bitwise equal between the layouts."""
+    (basis, y) bitwise equal between the layouts.  ChebPlan.stream_dispatch
+    says which layout a variant really takes: B = 48 (CB = 48: 12, 24 or 48
+    lanes) is refused by the wide layout, so that case runs the sample-major
+    steps under both variants (narrow under both: only its comparison with the
+    oracle says anything); B = 16 is the wide batch that is no multiple of 32."""
     from cnn_graph_amd import ops
     from cnn_graph_amd.plan import ChebPlan
     rp, ci, v, M = graph_c["Lt_rowptr"], graph_c["Lt_col"], graph_c["Lt_val"], graph_c["M"]
@@ -100,6 +107,8 @@ def test_config_c_wide_vs_narrow_layout(dev, graph_c, N, Fin, K, Fout):
     for variant in ("auto", "narrow"):
         plan = ChebPlan(scipy.sparse.csr_matrix((v, ci, rp), shape=(M, M)), device=0, variant=variant)
         assert plan.query_path(N, Fin, K, Fout) == "stream"
+        is_wide = variant == "auto" and N * Fin != 48
+        assert plan.stream_dispatch(N, Fin, K, Fout)["wide"] == int(is_wide), (variant, N, Fin)
         basis, y = ops.cheb_forward(plan, t(x, dev), t(W, dev), K)
         dx, dW = ops.cheb_backward(plan, t(dy, dev), basis, t(W, dev), K)
         dxa = t(dx0, dev)
