@@ -386,36 +386,6 @@ int check_layout(const cg_plan* p, int32_t Fin, int32_t K, int32_t Fout, int lay
   return CG_OK;
 }
 
-struct StreamWs {
-  bool wide;     // wide-column layout (cheb_wide.hip) for small Fin
-  size_t slots;  // forward: T_1 .. T_{K-2} (sample-major), or the K planes T_0 .. T_{K-1} ([M][B], wide)
-  size_t dA;     // backward: dBasis, N*M*FinK floats (k-major); G_k overwrites plane k
-                 // (wide: + the same again for the [K][M][B] planes D_k / G_k)
-};
-
-// The wide-column path serves the streaming path when Fin < 8 (sample-major
-// gathers of Fin*4 < 32 bytes) and its column split fits (cheb_wide.hip).
-bool use_wide(const cg_plan* p, int32_t N, int32_t Fin, int32_t K) {
-  return p->variant != CG_VARIANT_NARROW && int64_t(Fin) * K <= 256 &&
-         cg::wide_geometry(N, Fin, p->M).ok;
-}
-
-StreamWs stream_ws(const cg_plan* p, int32_t N, int32_t Fin, int32_t K, int32_t Fout) {
-  StreamWs w{};
-  const int64_t B = int64_t(N) * Fin;
-  const int64_t FinK = int64_t(Fin) * K;
-  const int64_t NM = int64_t(N) * p->M;
-  w.wide = use_wide(p, N, Fin, K);
-  const size_t plane = size_t(p->M) * size_t(B) * 4;
-  w.slots = al256(w.wide ? size_t(K) * plane : size_t(K > 2 ? K - 2 : 0) * plane);
-  w.dA = al256(size_t(NM) * size_t(FinK) * 4);
-  // wide: the [K][M][B] planes D_k / G_k (+ the sample-major dBasis when the
-  // fused dy pass does not apply)
-  if (w.wide) w.dA = al256(size_t(K) * plane) + (cg::wide_dypass_ok(int(FinK), Fout) ? 0 : w.dA);
-  (void)Fout;
-  return w;
-}
-
 // dW partial slabs: dw_chunks(R) of them from k_dw_slabs, or one per sample
 // from the fused backward.
 // M > 0: the wide path's fused dy pass writes the slabs (one per block)
@@ -425,81 +395,168 @@ size_t dw_slab_bytes(int64_t R, int32_t N, int FinK, int Fout, int32_t M = 0) {
   return al256(n * size_t(FinK) * size_t(Fout) * 4);
 }
 
-// Channel-group resident kernels (cheb_group.hip) serve the sample-major
-// streaming path for M <= 1024, Fin % 8 == 0 (forward: planes layout only).
-bool use_group(const cg_plan* p, int32_t Fin, int32_t K, int32_t Fout) {
-  return p->variant != CG_VARIANT_STEPS && p->variant != CG_VARIANT_NARROW &&
-         cg::grp_ok(p->M, std::max(p->nnz, p->nnzT), Fin, K, Fout);
-}
+// What a Chebyshev convolution launches and where its buffers lie, decided once
+// per call by cheb_route.  The forward, the backward, cg_cheb_workspace_bytes and
+// the test hook cg_plan_query_stream_dispatch all read it, so they cannot
+// disagree.  A field that does not apply is zero (last_staged: -1).  What depends
+// on the call's pointers or the ablation build stays with backward_impl /
+// forward_impl: dw_small_aligned(basis, dy), the cg::debug_flags() bits, x != basis.
+enum class FwdKind { Fast, Resident, Copy, WideSteps, Group, PlanesSteps, Steps };
+enum class BwdKind { Fast, Resident, WideDypass, GroupDy, WidePlanes, GroupPlanes, Clenshaw };
+// dBasis = dy W^T of the backwards that read dBasis planes
+enum class DaGemm { None, RowAllPlanes, RowPerPlane, Gemm };
+// y = act(basis W + res) after the forward recurrence
+enum class YGemm { InKernel, RowPlanes, Row, GemmThenAct };
 
-// Workspace layout.  forward: [T_1 .. T_{K-2}] (streaming path only).
-// backward: [dW slabs][dBasis] (dBasis for the streaming path only; the
-// reverse recurrence writes G_k over plane k of it, so it needs no ring).
-// The forward's workspace is dead once the forward has returned, so one
-// buffer of max(fwd, bwd) bytes may serve both.
-int workspace_bytes(const cg_plan* p, int32_t N, int32_t Fin, int32_t K, int32_t Fout,
-                    size_t* fwd, size_t* bwd) {
-  int pf = 0, pb = 0, rc;
-  if ((rc = choose_path(p, Fin, K, Fout, false, &pf))) return rc;
-  if ((rc = choose_path(p, Fin, K, Fout, true, &pb))) return rc;
-  const StreamWs w = stream_ws(p, N, Fin, K, Fout);
-  const bool dypass = pb != CG_PATH_RESIDENT && stream_ws(p, N, Fin, K, Fout).wide &&
-                      cg::wide_dypass_ok(Fin * K, Fout);
-  const size_t slabs = dw_slab_bytes(int64_t(N) * p->M, N, Fin * K, Fout, dypass ? p->M : 0);
-  *fwd = (pf == CG_PATH_RESIDENT) ? 0 : w.slots;
-  if (pf != CG_PATH_RESIDENT && use_group(p, Fin, K, Fout))  // per-group partial y (planes layout)
-    *fwd = std::max(*fwd, al256(cg::grp_partial_bytes(N, p->M, Fin, Fout)));
-  *bwd = slabs + ((pb == CG_PATH_RESIDENT) ? 0 : w.dA);
+struct ChebRoute {
+  int path_fwd, path_bwd;  // CG_PATH_RESIDENT / CG_PATH_STREAM
+  FwdKind fwd;             // the forward recurrence
+  BwdKind bwd;             // the backward dx pass
+  bool wide;               // streaming path in the wide-column layout (cheb_wide.hip)
+  bool fused_last;         // WideSteps: k_wide_last (last step fused with the assembly)
+  int assemble_tm;         // WideSteps: rows per tile of k_wide_assemble (0: not launched)
+  int dypass;              // WideDypass: 1 k_wide_dypass_small, 2 k_wide_dypass
+  int last_staged;         // Steps: 1 k_cheb_last (LDS staged), 0 k_cheb_step<., true>
+  const int* rperm_fwd;    // row order of the forward / backward steps (NULL: natural,
+  const int* rperm_bwd;    // or no stepping kernel)
+  DaGemm da_gemm;
+  YGemm y_gemm;
+  bool dw_fused;  // Fast backward forms the dW slabs (when the call wants dx and dW)
+  bool dw_small;  // dW in one block (rows layout, aligned pointers)
+  int vec;        // sample-major steps: floats per lane
+  cg::StepGeom step;
+  cg::WideGeom wg;
+  cg::FastGeom fast;
+  cg::ResidentGeom res;
+  // Workspace.  forward: T_1 .. T_{K-2} (sample-major), the K planes T_0 .. T_{K-1}
+  // (wide) or the per-group partial y; the size holds for every layout the shape
+  // admits.  backward: [dW slabs][dBasis][wide D planes] (streaming path; G_k
+  // overwrites plane k, so no ring).  The forward's workspace is dead once it has
+  // returned, so one buffer of max(fwd, bwd) bytes may serve both.
+  size_t fwd_bytes, bwd_bytes;
+  size_t off_dA, off_D;  // byte offsets inside the backward workspace (the dW slabs: 0)
+};
+
+// The only place where the dispatch predicates are combined.  `layout` has
+// passed check_layout.  with_bwd = false (the forward) leaves the backward half
+// unset, so a forward still runs where only the backward fails to fit a forced
+// resident path.
+int cheb_route(const cg_plan* p, int32_t N, int32_t Fin, int32_t K, int32_t Fout, int layout,
+               bool with_bwd, ChebRoute* out) {
+  ChebRoute& r = *out = ChebRoute{};
+  r.last_staged = -1;
+  int rc;
+  if ((rc = choose_path(p, Fin, K, Fout, false, &r.path_fwd))) return rc;
+  if (with_bwd && (rc = choose_path(p, Fin, K, Fout, true, &r.path_bwd))) return rc;
+  const int M = p->M, FinK = Fin * K;
+  const int64_t R = int64_t(N) * M;
+  const bool stream_f = r.path_fwd == CG_PATH_STREAM;
+  const bool stream_b = with_bwd && r.path_bwd == CG_PATH_STREAM;
+  bool group = false;
+  if (stream_f || stream_b) {
+    // The wide-column layout serves the streaming path when Fin < 8 (sample-major
+    // gathers of Fin*4 < 32 bytes) and its column split fits (cheb_wide.hip).
+    const cg::WideGeom wg = cg::wide_geometry(N, Fin, M);
+    r.wide = p->variant != CG_VARIANT_NARROW && int64_t(Fin) * K <= 256 && wg.ok;
+    if (r.wide) {
+      r.wg = wg;
+    } else {
+      r.vec = cg::step_vec(Fin);
+      r.step = cg::step_geom(N, M, Fin, r.vec);
+      // Channel-group resident kernels (cheb_group.hip) serve the sample-major
+      // streaming path for M <= 1024, Fin % 8 == 0 (forward: planes layout only).
+      group = p->variant != CG_VARIANT_STEPS && p->variant != CG_VARIANT_NARROW &&
+              cg::grp_ok(M, std::max(p->nnz, p->nnzT), Fin, K, Fout);
+    }
+  }
+  const bool fast_f = layout == CG_BASIS_ORDERS ||
+                      (r.path_fwd == CG_PATH_RESIDENT && use_fast(p, Fin, K, Fout, false));
+  const bool fast_b = with_bwd && r.path_bwd == CG_PATH_RESIDENT && use_fast(p, Fin, K, Fout, true);
+  if (fast_f || fast_b) r.fast = fast_geom(p, Fin, K, Fout);
+  if ((!fast_f && !stream_f) || (with_bwd && !fast_b && !stream_b))
+    r.res = cg::resident_geometry(M, int(p->nnz), p->max_row_nnz, p->max_row_nnzT, Fin, K, Fout);
+
+  if (fast_f) {
+    r.fwd = FwdKind::Fast;
+  } else if (!stream_f) {
+    r.fwd = FwdKind::Resident;
+  } else if (K == 1) {
+    r.fwd = FwdKind::Copy;
+  } else if (r.wide) {
+    r.fwd = FwdKind::WideSteps;
+    r.rperm_fwd = p->rperm;
+    r.fused_last = cg::wide_last_ok(r.wg, Fin, K, p->rperm != nullptr);
+    r.assemble_tm = r.fused_last ? 0 : cg::wide_tm(FinK);
+  } else if (layout == CG_BASIS_PLANES && group) {
+    r.fwd = FwdKind::Group;
+  } else {
+    r.fwd = layout == CG_BASIS_PLANES ? FwdKind::PlanesSteps : FwdKind::Steps;
+    r.rperm_fwd = cg::step_rperm(p->rperm, Fin);
+    if (r.fwd == FwdKind::Steps)  // (planes: every step writes its own plane)
+      r.last_staged = cg::cheb_last_stage_bytes(r.step, Fin, K) <= size_t(cg::kLdsBytes) ? 1 : 0;
+  }
+  if (fast_f || !stream_f || r.fwd == FwdKind::Group) r.y_gemm = YGemm::InKernel;
+  else if (layout == CG_BASIS_PLANES) r.y_gemm = YGemm::RowPlanes;
+  else r.y_gemm = cg::rowgemm_ok(FinK, FinK, Fout) ? YGemm::Row : YGemm::GemmThenAct;
+  const size_t plane = size_t(M) * size_t(int64_t(N) * Fin) * 4;
+  if (stream_f) {
+    r.fwd_bytes = al256(r.wide ? size_t(K) * plane : size_t(K > 2 ? K - 2 : 0) * plane);
+    if (group) r.fwd_bytes = std::max(r.fwd_bytes, al256(cg::grp_partial_bytes(N, M, Fin, Fout)));
+  }
+  if (!with_bwd) return CG_OK;
+
+  if (fast_b) {
+    r.bwd = BwdKind::Fast;
+    r.dw_fused = fused_dw(p, Fin, K, Fout);
+  } else if (!stream_b) {
+    r.bwd = BwdKind::Resident;
+  } else if (r.wide && cg::wide_dypass_ok(FinK, Fout)) {
+    r.bwd = BwdKind::WideDypass;
+    r.dypass = cg::wide_dypass_small(FinK) ? 1 : 2;
+  } else if (group && cg::grp_clen_dy_ok(M, p->nnzT, K, Fout)) {
+    r.bwd = BwdKind::GroupDy;
+  } else {
+    r.bwd = r.wide ? BwdKind::WidePlanes : group ? BwdKind::GroupPlanes : BwdKind::Clenshaw;
+    // all K planes in one pass over dy when the FinK columns fit one row-GEMM block
+    r.da_gemm = cg::rowgemm_ok(Fout, Fout, FinK)  ? DaGemm::RowAllPlanes
+                : cg::rowgemm_ok(Fout, Fout, Fin) ? DaGemm::RowPerPlane
+                                                  : DaGemm::Gemm;
+    if (r.bwd == BwdKind::Clenshaw) r.rperm_bwd = cg::step_rperm(p->trperm, Fin);
+  }
+  if (stream_b && r.wide && K >= 2) r.rperm_bwd = p->trperm;  // (K == 1: no step)
+  r.dw_small = cg::dw_small_ok(R, FinK, Fout);
+  // the fused dy pass writes the slabs itself, one per block
+  r.bwd_bytes = dw_slab_bytes(R, N, FinK, Fout, r.bwd == BwdKind::WideDypass ? M : 0);
+  r.off_dA = r.off_D = r.bwd_bytes;
+  if (stream_b) {
+    // dBasis, N*M*FinK floats (k-major); reported for GroupDy too, which forms it in LDS
+    if (r.bwd != BwdKind::WideDypass) r.bwd_bytes += al256(size_t(R) * size_t(FinK) * 4);
+    r.off_D = r.bwd_bytes;
+    if (r.wide) r.bwd_bytes += al256(size_t(K) * plane);  // the [K][M][B] planes D_k / G_k
+  }
   return CG_OK;
 }
 
-// What forward_impl / backward_impl launch on the streaming path, for the test
-// hook cg_plan_query_stream_dispatch: the branches of the two functions in
-// their order, decided by the predicates they call.  Host only, no launch.
+// The route of a shape whose forward and backward are both on the streaming
+// path, read out for the test hook cg_plan_query_stream_dispatch.
 // out: CG_SD_* of include/cheb_mi355_testing.h.
-void stream_dispatch(const cg_plan* p, int32_t N, int32_t Fin, int32_t K, int32_t Fout, int layout,
-                     int32_t* out) {
-  std::fill(out, out + CG_SD_COUNT, 0);
-  const int FinK = Fin * K;
-  const bool wide = stream_ws(p, N, Fin, K, Fout).wide;
-  out[CG_SD_WIDE] = wide;
-  out[CG_SD_LAST_STAGED] = -1;
-  if (wide) {
-    const cg::WideGeom g = cg::wide_geometry(N, Fin, p->M);
-    out[CG_SD_G] = g.G;
-    out[CG_SD_CB] = g.CB;
-    out[CG_SD_PL] = g.pl;
-    if (K >= 2) {  // (K == 1: the basis is a copy of x, no step)
-      const bool fused_last = cg::wide_last_ok(g, Fin, K, p->rperm != nullptr);
-      out[CG_SD_FUSED_LAST] = fused_last;
-      out[CG_SD_ASSEMBLE_TM] = fused_last ? 0 : cg::wide_tm(FinK);
-      out[CG_SD_SORTED_FWD] = p->rperm != nullptr;
-      out[CG_SD_SORTED_BWD] = p->trperm != nullptr;
-    }
-    if (cg::wide_dypass_ok(FinK, Fout)) out[CG_SD_DYPASS] = cg::wide_dypass_small(FinK) ? 1 : 2;
-    return;
-  }
-  const bool group = use_group(p, Fin, K, Fout);
-  const int vec = cg::step_vec(Fin);
-  const cg::StepGeom g = cg::step_geom(N, p->M, Fin, vec);
-  out[CG_SD_VEC] = vec;
-  out[CG_SD_LPR] = g.lpr;
-  out[CG_SD_RPW] = g.rpw;
-  out[CG_SD_XCD_MAP] = g.xcd_map;
-  if (K >= 2) {
-    if (layout == CG_BASIS_PLANES && group) {
-      out[CG_SD_GROUP_FWD] = 1;
-    } else {
-      out[CG_SD_SORTED_FWD] = cg::step_rperm(p->rperm, Fin) != nullptr;
-      if (layout != CG_BASIS_PLANES)  // (planes: every step writes its own plane)
-        out[CG_SD_LAST_STAGED] =
-            cg::cheb_last_stage_bytes(g, Fin, K) <= size_t(cg::kLdsBytes) ? 1 : 0;
-    }
-  }
-  if (group)
-    out[CG_SD_GROUP_BWD] = cg::grp_clen_dy_ok(p->M, p->nnzT, K, Fout) ? 2 : 1;
-  else
-    out[CG_SD_SORTED_BWD] = cg::step_rperm(p->trperm, Fin) != nullptr;
+void stream_dispatch(const ChebRoute& r, int32_t* out) {
+  out[CG_SD_WIDE] = r.wide;
+  out[CG_SD_G] = r.wg.G;
+  out[CG_SD_CB] = r.wg.CB;
+  out[CG_SD_PL] = r.wg.pl;
+  out[CG_SD_FUSED_LAST] = r.fused_last;
+  out[CG_SD_ASSEMBLE_TM] = r.assemble_tm;
+  out[CG_SD_DYPASS] = r.dypass;
+  out[CG_SD_SORTED_FWD] = r.rperm_fwd != nullptr;
+  out[CG_SD_SORTED_BWD] = r.rperm_bwd != nullptr;
+  out[CG_SD_GROUP_FWD] = r.fwd == FwdKind::Group;
+  out[CG_SD_GROUP_BWD] = r.bwd == BwdKind::GroupDy ? 2 : r.bwd == BwdKind::GroupPlanes ? 1 : 0;
+  out[CG_SD_VEC] = r.vec;
+  out[CG_SD_LPR] = r.step.lpr;
+  out[CG_SD_RPW] = r.step.rpw;
+  out[CG_SD_XCD_MAP] = r.step.xcd_map;
+  out[CG_SD_LAST_STAGED] = r.last_staged;
 }
 
 }  // namespace
@@ -509,7 +566,7 @@ namespace {
 // CG_OPT_* values (defaults: the measured-faster kernels) and their ranges
 std::atomic<int> g_opts[kOptCount] = {{1}, {1}, {8}, {1}, {1}, {1}, {1}, {1}, {1}, {1}};
 // The release library accepts only the values a user would choose between;
-// the alternatives that lost every A/B (DESIGN.md §5) exist in the ablation
+// the alternatives that lost every A/B (DESIGN.md §6) exist in the ablation
 // build only (`make debug`): CG_OPT_DW_DIRECT 2 / 3 (forced direct dW), CG_OPT_DW_W2
 // 0 (one-wave dW builds), CG_OPT_SPMM_PW 0, CG_OPT_GRP_PC 0, CG_OPT_CLEN_DY 0 / 2.
 bool option_valid(int o, int v) {
@@ -744,10 +801,10 @@ int cg_cheb_workspace_bytes(const cg_plan* plan, int32_t N, int32_t Fin, int32_t
                             size_t* fwd_bytes, size_t* bwd_bytes) {
   int rc = check_shape(plan, N, Fin, K, Fout);
   if (rc) return rc;
-  size_t f = 0, b = 0;
-  if ((rc = workspace_bytes(plan, N, Fin, K, Fout, &f, &b))) return rc;
-  if (fwd_bytes) *fwd_bytes = f;
-  if (bwd_bytes) *bwd_bytes = b;
+  ChebRoute r;
+  if ((rc = cheb_route(plan, N, Fin, K, Fout, CG_BASIS_ROWS, true, &r))) return rc;
+  if (fwd_bytes) *fwd_bytes = r.fwd_bytes;
+  if (bwd_bytes) *bwd_bytes = r.bwd_bytes;
   return ok();
 }
 
@@ -779,13 +836,11 @@ int forward_impl(cg_plan* plan, int32_t N, int32_t Fin, int32_t K, int32_t Fout,
   if (y && !W) return fail(CG_ERR_ARG, "null W with non-null y");
   if (!y && !basis) return fail(CG_ERR_ARG, "nothing to compute (basis and y both null)");
   if ((rc = check_device(plan))) return rc;
-  int path = 0;
-  if ((rc = choose_path(plan, Fin, K, Fout, false, &path))) return rc;
+  ChebRoute r;
+  if ((rc = cheb_route(plan, N, Fin, K, Fout, layout, false, &r))) return rc;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int M = plan->M;
-  const bool fast_fwd =
-      layout == CG_BASIS_ORDERS || (path == CG_PATH_RESIDENT && use_fast(plan, Fin, K, Fout, false));
-  if (fa && !fast_fwd) {
+  if (fa && r.fwd != FwdKind::Fast) {
     // other kernels: the same update out of place by k_adam, then the forward on W'
     const size_t nb = size_t(Fin) * K * Fout * sizeof(float);
     CG_HIP(hipMemcpyAsync(fa->W_out, W, nb, hipMemcpyDeviceToDevice, s));
@@ -797,21 +852,10 @@ int forward_impl(cg_plan* plan, int32_t N, int32_t Fin, int32_t K, int32_t Fout,
     fa = nullptr;
   }
 
-  if (fast_fwd) {
-    cg::FastFwdArgs a{};
-    a.M = M;
-    a.Fin = Fin;
-    a.K = K;
-    a.Fout = Fout;
-    a.dbg = cg::debug_flags() & 0xff;
-    a.E = plan->fast.view;
-    a.x = x;
-    a.W = y ? W : nullptr;
-    a.basis = basis;
-    a.y = y;
-    a.res = res;
-    a.act = act;
-    a.bord = layout == CG_BASIS_ORDERS ? basis_mb(M) : 0;
+  if (r.fwd == FwdKind::Fast) {
+    // (M, Fin, K, Fout, dbg, res, act, E, x, W, basis, y, bord)
+    cg::FastFwdArgs a{M, Fin, K, Fout, cg::debug_flags() & 0xff, res, act, plan->fast.view, x,
+                      y ? W : nullptr, basis, y, layout == CG_BASIS_ORDERS ? basis_mb(M) : 0};
 #ifdef CG_DEBUG
     a.ts = cg::g_debug_ts;
 #endif
@@ -829,107 +873,107 @@ int forward_impl(cg_plan* plan, int32_t N, int32_t Fin, int32_t K, int32_t Fout,
       a.ad_eps = fa->eps;
       a.ad_scale = fa->grad_scale;
     }
-    CG_HIP(cg::launch_fast_forward(fast_geom(plan, Fin, K, Fout), N, a, s));
+    CG_HIP(cg::launch_fast_forward(r.fast, N, a, s));
     return ok();
   }
-  if (path == CG_PATH_RESIDENT) {
-    const cg::ResidentGeom g = cg::resident_geometry(M, int(plan->nnz), plan->max_row_nnz, plan->max_row_nnzT, Fin, K, Fout);
-    cg::ResidentFwdArgs a{};
-    a.M = M;
-    a.Fin = Fin;
-    a.K = K;
-    a.Fout = Fout;
-    a.Mp = cg::lds_vertex_stride(M);
-    a.dbg = cg::debug_flags() & 0xff;
-    a.E = plan->slots.view;
-    a.col = plan->col;
-    a.val = plan->val;
-    a.x = x;
-    a.W = y ? W : nullptr;
-    a.basis = basis;
-    a.y = y;
-    a.res = res;
-    a.act = act;
-    CG_HIP(cg::launch_resident_forward(g, N, a, s));
+  if (r.fwd == FwdKind::Resident) {
+    // (M, Fin, K, Fout, Mp, dbg, res, act, E, col, val, x, W, basis, y)
+    const cg::ResidentFwdArgs a{M, Fin, K, Fout, cg::lds_vertex_stride(M), cg::debug_flags() & 0xff,
+                                res, act, plan->slots.view, plan->col, plan->val, x,
+                                y ? W : nullptr, basis, y};
+    CG_HIP(cg::launch_resident_forward(r.res, N, a, s));
     return ok();
   }
   // streaming path
   if (!basis) return fail(CG_ERR_ARG, "streaming path needs a basis buffer (the GEMM reads it)");
-  const StreamWs w = stream_ws(plan, N, Fin, K, Fout);
-  if (w.slots && (!workspace || ws_bytes < w.slots))
-    return fail(CG_ERR_ARG, "forward workspace too small: %zu < %zu", ws_bytes, w.slots);
+  if (r.fwd_bytes && (!workspace || ws_bytes < r.fwd_bytes))
+    return fail(CG_ERR_ARG, "forward workspace too small: %zu < %zu", ws_bytes, r.fwd_bytes);
   float* slots = static_cast<float*>(workspace);
   const size_t slot = size_t(M) * size_t(N) * size_t(Fin);
-  if (K == 1) {
-    if (x != basis) CG_HIP(hipMemcpyAsync(basis, x, slot * sizeof(float), hipMemcpyDeviceToDevice, s));
-  } else if (w.wide) {
-    // wide columns: T_0 = x re-laid [M][Fin*N] into plane 0, the K-1 steps
-    // plane to plane, then the basis (lib/graph_conv.py:155-172)
-    const cg::WideGeom g = cg::wide_geometry(N, Fin, M);
-    const int B = N * Fin;
-    const int* rperm = plan->rperm;
-    const bool fused_last = cg::wide_last_ok(g, Fin, K, rperm != nullptr);
-    CG_HIP(cg::launch_sm_to_vm(x, 1, N, int64_t(M) * Fin, slots, s));
-    for (int k = 1; k < (fused_last ? K - 1 : K); ++k)
-      CG_HIP(cg::launch_wide_step(g, plan->rowptr, plan->col, plan->val, rperm,
-                                  slots + size_t(k - 1) * slot,
-                                  k >= 2 ? slots + size_t(k - 2) * slot : nullptr, nullptr,
-                                  slots + size_t(k) * slot, M, B, k == 1 ? 0 : 1, 2.f, s));
-    if (fused_last)  // T_{K-1} and the basis assembly in one launch
-      CG_HIP(cg::launch_wide_last(g, plan->rowptr, plan->col, plan->val, slots, int64_t(slot), basis,
-                                  M, N, K, s));
-    else
-      CG_HIP(cg::launch_wide_assemble(slots, int64_t(slot), N, M, Fin, K, basis, s));
-  } else if (layout == CG_BASIS_PLANES && use_group(plan, Fin, K, Fout)) {
-    // channel-group resident kernel: the whole recurrence in LDS per (sample,
-    // 8 channels), planes written once, y from per-group MFMA partials
-    if (y && (!workspace || ws_bytes < cg::grp_partial_bytes(N, M, Fin, Fout)))
-      return fail(CG_ERR_ARG, "forward workspace too small for the group partials");
-    CG_HIP(cg::launch_grp_fwd(plan->rowptr, plan->col, plan->val, plan->lorder, plan->nnz, N, M, Fin, K,
-                              Fout, x,
-                              W, basis, static_cast<float*>(workspace), res, act, y, s));
-    return ok();
-  } else if (layout == CG_BASIS_PLANES) {
-    // planes layout: T_k IS plane k of the basis (plane 0 = x: copied unless
-    // the caller placed x there), every step writes its own plane, no assembly
-    // step (lib/graph_conv.py:159-169)
-    const int* rperm = cg::step_rperm(plan->rperm, Fin);
-    auto P = [&](int k) { return basis + size_t(k) * slot; };
-    if (x != basis) CG_HIP(hipMemcpyAsync(basis, x, slot * sizeof(float), hipMemcpyDeviceToDevice, s));
-    for (int k = 1; k < K; ++k)
-      CG_HIP(cg::launch_cheb_step(plan->rowptr, plan->col, plan->val, rperm, k == 1 ? x : P(k - 1),
-                                  k == 2 ? x : (k > 2 ? P(k - 2) : nullptr), P(k), x, nullptr,
-                                  nullptr, N, M, Fin, K, k, false, s));
-  } else {
-    // sample-major steps: T_0 = x, T_j (1 <= j <= K-2) in slots[j-1], the last
-    // step writes the whole basis (lib/graph_conv.py:159-172)
-    const int* rperm = cg::step_rperm(plan->rperm, Fin);
-    auto T = [&](int k) -> const float* { return k == 0 ? x : slots + size_t(k - 1) * slot; };
-    for (int k = 1; k < K; ++k) {
-      const bool last = (k == K - 1);
-      CG_HIP(cg::launch_cheb_step(plan->rowptr, plan->col, plan->val, rperm, T(k - 1),
-                                  k >= 2 ? T(k - 2) : nullptr,
-                                  last ? nullptr : slots + size_t(k - 1) * slot, x, slots, basis, N,
-                                  M, Fin, K, k, last, s));
+  switch (r.fwd) {
+    default:  // (Fast, Resident: returned above)
+      break;
+    case FwdKind::Copy:
+      if (x != basis) CG_HIP(hipMemcpyAsync(basis, x, slot * sizeof(float), hipMemcpyDeviceToDevice, s));
+      break;
+    case FwdKind::WideSteps: {
+      // wide columns: T_0 = x re-laid [M][Fin*N] into plane 0, the K-1 steps
+      // plane to plane, then the basis (lib/graph_conv.py:155-172)
+      const int B = N * Fin;
+      CG_HIP(cg::launch_sm_to_vm(x, 1, N, int64_t(M) * Fin, slots, s));
+      for (int k = 1; k < (r.fused_last ? K - 1 : K); ++k)
+        CG_HIP(cg::launch_wide_step(r.wg, plan->rowptr, plan->col, plan->val, r.rperm_fwd,
+                                    slots + size_t(k - 1) * slot,
+                                    k >= 2 ? slots + size_t(k - 2) * slot : nullptr, nullptr,
+                                    slots + size_t(k) * slot, M, B, k == 1 ? 0 : 1, 2.f, s));
+      if (r.fused_last)  // T_{K-1} and the basis assembly in one launch
+        CG_HIP(cg::launch_wide_last(r.wg, plan->rowptr, plan->col, plan->val, slots, int64_t(slot),
+                                    basis, M, N, K, s));
+      else
+        CG_HIP(cg::launch_wide_assemble(slots, int64_t(slot), N, M, Fin, K, basis, s));
+      break;
+    }
+    case FwdKind::Group:
+      // channel-group resident kernel: the whole recurrence in LDS per (sample,
+      // 8 channels), planes written once, y from per-group MFMA partials
+      CG_HIP(cg::launch_grp_fwd(plan->rowptr, plan->col, plan->val, plan->lorder, plan->nnz, N, M,
+                                Fin, K, Fout, x, W, basis, slots, res, act, y, s));
+      break;
+    case FwdKind::PlanesSteps: {
+      // planes layout: T_k IS plane k of the basis (plane 0 = x: copied unless
+      // the caller placed x there), every step writes its own plane, no assembly
+      // step (lib/graph_conv.py:159-169)
+      auto P = [&](int k) { return basis + size_t(k) * slot; };
+      if (x != basis) CG_HIP(hipMemcpyAsync(basis, x, slot * sizeof(float), hipMemcpyDeviceToDevice, s));
+      for (int k = 1; k < K; ++k)
+        CG_HIP(cg::launch_cheb_step(plan->rowptr, plan->col, plan->val, r.rperm_fwd,
+                                    k == 1 ? x : P(k - 1), k == 2 ? x : (k > 2 ? P(k - 2) : nullptr),
+                                    P(k), x, nullptr, nullptr, N, M, Fin, K, k, false, s));
+      break;
+    }
+    case FwdKind::Steps: {
+      // sample-major steps: T_0 = x, T_j (1 <= j <= K-2) in slots[j-1], the last
+      // step writes the whole basis (lib/graph_conv.py:159-172)
+      auto T = [&](int k) -> const float* { return k == 0 ? x : slots + size_t(k - 1) * slot; };
+      for (int k = 1; k < K; ++k) {
+        const bool last = (k == K - 1);
+        CG_HIP(cg::launch_cheb_step(plan->rowptr, plan->col, plan->val, r.rperm_fwd, T(k - 1),
+                                    k >= 2 ? T(k - 2) : nullptr,
+                                    last ? nullptr : slots + size_t(k - 1) * slot, x, slots, basis, N,
+                                    M, Fin, K, k, last, s));
+      }
+      break;
     }
   }
-  if (y && layout == CG_BASIS_PLANES) {
+  const int FinK = Fin * K;
+  if (!y || r.y_gemm == YGemm::InKernel) return ok();
+  if (r.y_gemm == YGemm::RowPlanes) {
     // y = sum_k T_k W_k straight from the planes (row GEMM, A addressed per plane)
-    const int FinK = Fin * K;
     CG_HIP(cg::launch_rowgemm(basis, int64_t(N) * M, FinK, FinK, W, Fout, 1, 0, 1, Fout, y, Fout, 0,
                               s, res, act, 0, Fin, int64_t(slot), K));
-  } else if (y) {
-    const int FinK = Fin * K;
-    if (cg::rowgemm_ok(FinK, FinK, Fout)) {
-      CG_HIP(cg::launch_rowgemm(basis, int64_t(N) * M, FinK, FinK, W, Fout, 1, 0, 1, Fout, y, Fout,
-                                0, s, res, act));
-    } else {
-      CG_HIP(cg::launch_gemm_f32(false, false, N * M, Fout, FinK, basis, FinK, W, Fout, y, Fout, 1,
-                                 s));
-      if (res || act) CG_HIP(cg::launch_act_fwd(y, res, act, int64_t(N) * M * Fout, s));
-    }
+  } else if (r.y_gemm == YGemm::Row) {
+    CG_HIP(cg::launch_rowgemm(basis, int64_t(N) * M, FinK, FinK, W, Fout, 1, 0, 1, Fout, y, Fout, 0,
+                              s, res, act));
+  } else {
+    CG_HIP(cg::launch_gemm_f32(false, false, N * M, Fout, FinK, basis, FinK, W, Fout, y, Fout, 1, s));
+    if (res || act) CG_HIP(cg::launch_act_fwd(y, res, act, int64_t(N) * M * Fout, s));
   }
   return ok();
+}
+
+// Wide-column reverse recurrence over the [K][M][Fin*N] planes D: G_k in place
+// of D_k, one launch per step (G_{K-1} = D_{K-1}: the last order's step would
+// rewrite its plane in place), then G_0 re-laid into dx (dx += when accumulating)
+int wide_reverse(const cg_plan* plan, const ChebRoute& r, float* D, int32_t N, int32_t Fin,
+                 int32_t K, float* dx, int dx_acc, hipStream_t s) {
+  const int M = plan->M, B = N * Fin;
+  auto G = [&](int k) { return D + size_t(k) * size_t(M) * size_t(B); };
+  for (int k = K - 2; k >= 0; --k)
+    CG_HIP(cg::launch_wide_step(r.wg, plan->trowptr, plan->tcol, plan->tval, r.rperm_bwd, G(k + 1),
+                                (k + 2 <= K - 1) ? G(k + 2) : nullptr, G(k), G(k), M, B, 2,
+                                k >= 1 ? 2.f : 1.f, s));
+  CG_HIP(cg::launch_vm_to_sm(G(0), N, int64_t(M) * Fin, dx, dx_acc, s));
+  return CG_OK;
 }
 
 int backward_impl(cg_plan* plan, int32_t N, int32_t Fin, int32_t K, int32_t Fout, const float* dy,
@@ -945,153 +989,98 @@ int backward_impl(cg_plan* plan, int32_t N, int32_t Fin, int32_t K, int32_t Fout
   if (!basis && dW) return fail(CG_ERR_ARG, "null basis: dW needs the forward's basis");
   if (!dx && !dW) return fail(CG_ERR_ARG, "dx and dW are both NULL: nothing to compute");
   if ((rc = check_device(plan))) return rc;
-  int path = 0;
-  if ((rc = choose_path(plan, Fin, K, Fout, true, &path))) return rc;
-  size_t need_f = 0, need_b = 0;
-  if ((rc = workspace_bytes(plan, N, Fin, K, Fout, &need_f, &need_b))) return rc;
-  if (!workspace || ws_bytes < need_b)
-    return fail(CG_ERR_ARG, "backward workspace too small: %zu < %zu", ws_bytes, need_b);
+  ChebRoute r;
+  if ((rc = cheb_route(plan, N, Fin, K, Fout, layout, true, &r))) return rc;
+  if (!workspace || ws_bytes < r.bwd_bytes)
+    return fail(CG_ERR_ARG, "backward workspace too small: %zu < %zu", ws_bytes, r.bwd_bytes);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int M = plan->M;
   const int FinK = Fin * K;
   const int64_t R = int64_t(N) * M;
-  const int chunks = cg::dw_chunks(R);
 
   // Everything runs on the caller's stream.  (Forking the streaming dW GEMM onto a side stream to
   // overlap the dx recurrence was measured on MI355X in round 1: the event
   // fork + join costs ~20 us per call, more than the overlap gains there.)
   char* base = static_cast<char*>(workspace);
   float* slabs = reinterpret_cast<float*>(base);
-  const bool dypass = path != CG_PATH_RESIDENT && stream_ws(plan, N, Fin, K, Fout).wide &&
-                      cg::wide_dypass_ok(FinK, Fout);
-  char* rest = base + dw_slab_bytes(R, N, FinK, Fout, dypass ? M : 0);
-  const bool fused =
-      dx != nullptr && dW != nullptr && path == CG_PATH_RESIDENT && fused_dw(plan, Fin, K, Fout);
+  float* dA = reinterpret_cast<float*>(base + r.off_dA);  // dBasis, k-major [K][N*M][Fin]
+  float* D = reinterpret_cast<float*>(base + r.off_D);    // wide: the [K][M][Fin*N] planes D_k / G_k
+  const size_t slot = size_t(M) * size_t(N) * size_t(Fin);
+  const bool fused = dx != nullptr && dW != nullptr && r.dw_fused;
   int nslab_ready = 0;  // dW slabs a kernel of the dx pass already wrote
-  auto launch_dw = [&](hipStream_t st) -> hipError_t {
-    if (cg::debug_flags() & (1 << 22)) return hipSuccess;  // ablation hook (debug build): skip dW
-    return cg::launch_dw_slabs(basis, dy, R, FinK, Fout, slabs, st,
-                               layout == CG_BASIS_PLANES ? Fin : 0,
-                               layout == CG_BASIS_PLANES ? int64_t(R) * Fin : 0, K);
-  };
   if (dx) {
-    if (path == CG_PATH_RESIDENT && use_fast(plan, Fin, K, Fout, true)) {
-      const cg::FastGeom g = fast_geom(plan, Fin, K, Fout);
-      cg::FastBwdArgs a{};
-      a.M = M;
-      a.Fin = Fin;
-      a.K = K;
-      a.Fout = Fout;
-      a.Mp = cg::lds_vertex_stride(M);
-      a.dbg = (cg::debug_flags() >> 8) & 0xff;
-      a.dscratch_bytes = g.dscratch;
-      a.E = plan->tfast.view;
-      a.dy = dy;
-      a.basis = basis;
-      a.W = W;
-      a.dx = dx;
-      a.dx_acc = dx_acc;
-      a.dw_slab = fused ? slabs : nullptr;
-      a.bord = layout == CG_BASIS_ORDERS ? basis_mb(M) : 0;
-      a.x3 = cg::option(cg::kOptGemmX3) != 0 ? 1 : 0;
+    // dBasis = dy W^T written k-major ([K][N*M][Fin]): plane k is
+    // dA_k[r][fin] = sum_f dy[r][f] W[fin*K+k][f]
+    const int NM = N * M;
+    if (r.da_gemm == DaGemm::RowAllPlanes)
+      CG_HIP(cg::launch_rowgemm(dy, NM, Fout, Fout, W, 1, int64_t(K) * Fout, Fout, 1, FinK, dA, Fin,
+                                int64_t(slot), s, nullptr, 0, Fin));
+    else if (r.da_gemm == DaGemm::RowPerPlane)
+      CG_HIP(cg::launch_rowgemm(dy, NM, Fout, Fout, W, 1, int64_t(K) * Fout, Fout, K, Fin, dA, Fin,
+                                int64_t(slot), s));
+    else if (r.da_gemm == DaGemm::Gemm)
+      CG_HIP(cg::launch_gemm_f32(false, true, NM, FinK, Fout, dy, Fout, W, Fout, dA, FinK, 1, s, K));
+    switch (r.bwd) {
+      case BwdKind::Fast: {
+        // (M, Fin, K, Fout, Mp, dbg, dx_acc, dscratch_bytes, E, dy, basis, W, dx, dw_slab, bord)
+        cg::FastBwdArgs a{M, Fin, K, Fout, cg::lds_vertex_stride(M), (cg::debug_flags() >> 8) & 0xff,
+                          dx_acc, r.fast.dscratch, plan->tfast.view, dy, basis, W, dx,
+                          fused ? slabs : nullptr, layout == CG_BASIS_ORDERS ? basis_mb(M) : 0};
+        a.x3 = cg::option(cg::kOptGemmX3) != 0 ? 1 : 0;
 #ifdef CG_DEBUG
-      a.ts = cg::g_debug_ts;
+        a.ts = cg::g_debug_ts;
 #endif
-      CG_HIP(cg::launch_fast_backward(g, N, a, s));
-    } else if (path == CG_PATH_RESIDENT) {
-      const cg::ResidentGeom g = cg::resident_geometry(M, int(plan->nnz), plan->max_row_nnz,
-                                                       plan->max_row_nnzT, Fin, K, Fout);
-      cg::ResidentBwdArgs a{};
-      a.M = M;
-      a.Fin = Fin;
-      a.K = K;
-      a.Fout = Fout;
-      a.Mp = cg::lds_vertex_stride(M);
-      a.dbg = (cg::debug_flags() >> 8) & 0xff;
-      a.E = plan->tslots.view;
-      a.col = plan->tcol;
-      a.val = plan->tval;
-      a.dy = dy;
-      a.W = W;
-      a.dx = dx;
-      a.dx_acc = dx_acc;
-      CG_HIP(cg::launch_resident_backward(g, N, a, s));
-    } else if (dypass) {
-      // wide columns: ONE pass over dy writes the D_k planes straight in the
-      // [M][Fin*N] layout and the dW slabs; then G_k in place of D_k, one
-      // launch per step, and G_0 re-laid into dx (dx += when accumulating)
-      const cg::WideGeom g = cg::wide_geometry(N, Fin, M);
-      const int B = N * Fin;
-      const size_t slot = size_t(M) * size_t(B);
-      float* D = reinterpret_cast<float*>(rest);
-      CG_HIP(cg::launch_wide_dypass(dy, basis, W, N, M, Fin, K, Fout, D, int64_t(slot),
-                                    dW ? slabs : nullptr, s));
-      if (dW) nslab_ready = cg::wide_dypass_blocks(N, M);
-      auto G = [&](int k) { return D + size_t(k) * slot; };
-      // (G_{K-1} = D_{K-1}: the last order's step would rewrite its plane in place)
-      for (int k = K - 2; k >= 0; --k)
-        CG_HIP(cg::launch_wide_step(g, plan->trowptr, plan->tcol, plan->tval, plan->trperm,
-                                    (k + 1 <= K - 1) ? G(k + 1) : nullptr,
-                                    (k + 2 <= K - 1) ? G(k + 2) : nullptr, G(k), G(k), M, B, 2,
-                                    k >= 1 ? 2.f : 1.f, s));
-      CG_HIP(cg::launch_vm_to_sm(G(0), N, int64_t(M) * Fin, dx, dx_acc, s));
-    } else if (!stream_ws(plan, N, Fin, K, Fout).wide && use_group(plan, Fin, K, Fout) &&
-               cg::grp_clen_dy_ok(M, plan->nnzT, K, Fout)) {
-      // the whole reverse recurrence in LDS per (sample, 8 channels), dBasis
-      // formed in the kernel from dy and W (no dBasis planes)
-      CG_HIP(cg::launch_grp_clen_dy(plan->trowptr, plan->tcol, plan->tval, plan->tlorder, plan->nnzT,
-                                    N, M, Fin, K, Fout, dy, W, dx, dx_acc, s));
-    } else {
-      float* dA = reinterpret_cast<float*>(rest);
-      const int NM = N * M;
-      // dBasis = dy W^T written k-major ([K][N*M][Fin]), then the reverse
-      // recurrence one launch per step in the sample-major layout.  Step k
-      // reads D_k[r] and writes G_k[r] at the same address (same lane), and
-      // the steps below k gather G_{k+1} / read G_{k+2} from planes k+1 / k+2,
-      // so G lives in place of dBasis: no separate ring (for config D at
-      // N = 256 that is 3 x 17.2 GB less workspace).
-      const size_t slot = size_t(M) * size_t(N) * size_t(Fin);
-      // plane k: dA_k[r][fin] = sum_f dy[r][f] W[fin*K+k][f]; all K planes in
-      // one pass over dy when the FinK columns fit one row-GEMM block
-      if (cg::rowgemm_ok(Fout, Fout, FinK))
-        CG_HIP(cg::launch_rowgemm(dy, NM, Fout, Fout, W, 1, int64_t(K) * Fout, Fout, 1, FinK, dA, Fin,
-                                  int64_t(slot), s, nullptr, 0, Fin));
-      else if (cg::rowgemm_ok(Fout, Fout, Fin))
-        CG_HIP(cg::launch_rowgemm(dy, NM, Fout, Fout, W, 1, int64_t(K) * Fout, Fout, K, Fin, dA, Fin,
-                                  int64_t(slot), s));
-      else
-        CG_HIP(cg::launch_gemm_f32(false, true, NM, FinK, Fout, dy, Fout, W, Fout, dA, FinK, 1, s, K));
-      const StreamWs w = stream_ws(plan, N, Fin, K, Fout);
-      if (w.wide) {
-        // wide columns: the k-planes re-laid [M][Fin*N], then G_k in place of
-        // D_k one launch per step, G_0 re-laid into dx (dx += when accumulating)
-        const cg::WideGeom g = cg::wide_geometry(N, Fin, M);
-        const int B = N * Fin;
-        float* D = reinterpret_cast<float*>(rest + al256(size_t(R) * size_t(FinK) * 4));
+        CG_HIP(cg::launch_fast_backward(r.fast, N, a, s));
+        break;
+      }
+      case BwdKind::Resident: {
+        // (M, Fin, K, Fout, Mp, dbg, dx_acc, E, col, val, dy, W, dx)
+        const cg::ResidentBwdArgs a{M, Fin, K, Fout, cg::lds_vertex_stride(M),
+                                    (cg::debug_flags() >> 8) & 0xff, dx_acc, plan->tslots.view,
+                                    plan->tcol, plan->tval, dy, W, dx};
+        CG_HIP(cg::launch_resident_backward(r.res, N, a, s));
+        break;
+      }
+      case BwdKind::WideDypass:
+        // wide columns: ONE pass over dy writes the D_k planes straight in the
+        // [M][Fin*N] layout and the dW slabs
+        CG_HIP(cg::launch_wide_dypass(dy, basis, W, N, M, Fin, K, Fout, D, int64_t(slot),
+                                      dW ? slabs : nullptr, s));
+        if (dW) nslab_ready = cg::wide_dypass_blocks(N, M);
+        if ((rc = wide_reverse(plan, r, D, N, Fin, K, dx, dx_acc, s))) return rc;
+        break;
+      case BwdKind::WidePlanes:
+        // wide columns: the k-planes of dBasis re-laid [M][Fin*N]
         CG_HIP(cg::launch_sm_to_vm(dA, K, N, int64_t(M) * Fin, D, s));
-        auto G = [&](int k) { return D + size_t(k) * slot; };
-        for (int k = K - 2; k >= 0; --k)  // (G_{K-1} = D_{K-1} in place: no step)
-          CG_HIP(cg::launch_wide_step(g, plan->trowptr, plan->tcol, plan->tval, plan->trperm,
-                                      (k + 1 <= K - 1) ? G(k + 1) : nullptr,
-                                      (k + 2 <= K - 1) ? G(k + 2) : nullptr, G(k), G(k), M, B, 2,
-                                      k >= 1 ? 2.f : 1.f, s));
-        CG_HIP(cg::launch_vm_to_sm(G(0), N, int64_t(M) * Fin, dx, dx_acc, s));
-      } else if (use_group(plan, Fin, K, Fout)) {
+        if ((rc = wide_reverse(plan, r, D, N, Fin, K, dx, dx_acc, s))) return rc;
+        break;
+      case BwdKind::GroupDy:
+        // the whole reverse recurrence in LDS per (sample, 8 channels), dBasis
+        // formed in the kernel from dy and W (no dBasis planes)
+        CG_HIP(cg::launch_grp_clen_dy(plan->trowptr, plan->tcol, plan->tval, plan->tlorder,
+                                      plan->nnzT, N, M, Fin, K, Fout, dy, W, dx, dx_acc, s));
+        break;
+      case BwdKind::GroupPlanes:
         // the whole reverse recurrence in LDS per (sample, 8 channels)
-        CG_HIP(cg::launch_grp_clen(plan->trowptr, plan->tcol, plan->tval, plan->tlorder, plan->nnzT, N,
-                                   M, Fin, K,
-                                   dA, dx, dx_acc, s));
-      } else {
-        const int* rperm = cg::step_rperm(plan->trperm, Fin);
+        CG_HIP(cg::launch_grp_clen(plan->trowptr, plan->tcol, plan->tval, plan->tlorder, plan->nnzT,
+                                   N, M, Fin, K, dA, dx, dx_acc, s));
+        break;
+      case BwdKind::Clenshaw: {
+        // the reverse recurrence one launch per step in the sample-major
+        // layout.  Step k reads D_k[r] and writes G_k[r] at the same address
+        // (same lane), and the steps below k gather G_{k+1} / read G_{k+2} from
+        // planes k+1 / k+2, so G lives in place of dBasis: no separate ring (for
+        // config D at N = 256 that is 3 x 17.2 GB less workspace).
         auto G = [&](int k) { return dA + size_t(k) * slot; };
-        // G_{K-1} = D_{K-1} already sits in its plane (G lives in place of D):
-        // the last order's step would only rewrite it (D's 17 GB at N = 256);
-        // with K = 1 the one step is dx = D_0
+        // G_{K-1} = D_{K-1} already sits in its plane: the last order's step
+        // would only rewrite it (D's 17 GB at N = 256); with K = 1 the one step
+        // is dx = D_0
         for (int k = K >= 2 ? K - 2 : 0; k >= 0; --k)
-          CG_HIP(cg::launch_clenshaw(plan->trowptr, plan->tcol, plan->tval, rperm,
+          CG_HIP(cg::launch_clenshaw(plan->trowptr, plan->tcol, plan->tval, r.rperm_bwd,
                                      (k + 1 <= K - 1) ? G(k + 1) : nullptr,
                                      (k + 2 <= K - 1) ? G(k + 2) : nullptr, k == 0 ? dx : G(k),
                                      G(k), N, M, Fin, K, k, dx_acc, s));
+        break;
       }
     }
   }
@@ -1099,14 +1088,17 @@ int backward_impl(cg_plan* plan, int32_t N, int32_t Fin, int32_t K, int32_t Fout
   if (fused) nslab_ready = N;
   // small problems (config A): dW in one block, no slabs and no reduction
   // launch (with Adam: the one result is the single slab of the fused reduction)
-  if (!nslab_ready && layout == CG_BASIS_ROWS && cg::dw_small_ok(R, FinK, Fout) &&
-      cg::dw_small_aligned(basis, dy) && !(cg::debug_flags() & (1 << 22))) {
+  if (!nslab_ready && layout == CG_BASIS_ROWS && r.dw_small && cg::dw_small_aligned(basis, dy) &&
+      !(cg::debug_flags() & (1 << 22))) {
     CG_HIP(cg::launch_dw_small(basis, dy, R, FinK, Fout, adam ? slabs : dW, s));
     if (!adam) return ok();
     nslab_ready = 1;
   }
-  if (!nslab_ready) CG_HIP(launch_dw(s));
-  const int nslab = nslab_ready ? nslab_ready : chunks;
+  if (!nslab_ready && !(cg::debug_flags() & (1 << 22)))  // ablation hook (debug build): skip dW
+    CG_HIP(cg::launch_dw_slabs(basis, dy, R, FinK, Fout, slabs, s,
+                               layout == CG_BASIS_PLANES ? Fin : 0,
+                               layout == CG_BASIS_PLANES ? int64_t(R) * Fin : 0, K));
+  const int nslab = nslab_ready ? nslab_ready : cg::dw_chunks(R);
   if (adam)  // reduction + optimizer step in one launch (no exchange in between)
     CG_HIP(cg::launch_reduce_slabs_adam(slabs, nslab, int64_t(FinK) * Fout, dW, *adam, s));
   else if (!(cg::debug_flags() & (1 << 23)))  // ablation hook (debug build): skip the reduction
@@ -1987,13 +1979,12 @@ int cg_plan_query_stream_dispatch(const cg_plan* plan, int32_t N, int32_t Fin, i
   if (rc) return rc;
   if (!out) return fail(CG_ERR_ARG, "null dispatch out-pointer");
   if ((rc = check_layout(plan, Fin, K, Fout, layout))) return rc;
-  int pf = 0, pb = 0;
-  if ((rc = choose_path(plan, Fin, K, Fout, false, &pf))) return rc;
-  if ((rc = choose_path(plan, Fin, K, Fout, true, &pb))) return rc;
-  if (pf != CG_PATH_STREAM || pb != CG_PATH_STREAM)
+  ChebRoute r;
+  if ((rc = cheb_route(plan, N, Fin, K, Fout, layout, true, &r))) return rc;
+  if (r.path_fwd != CG_PATH_STREAM || r.path_bwd != CG_PATH_STREAM)
     return fail(CG_ERR_UNSUPPORTED, "not on the streaming path: M=%d Fin=%d K=%d Fout=%d", plan->M,
                 Fin, K, Fout);
-  stream_dispatch(plan, N, Fin, K, Fout, layout, out);
+  stream_dispatch(r, out);
   return ok();
 }
 

@@ -23,8 +23,8 @@ int cg_plan_set_seq_fault_test(cg_plan* plan, int32_t step);
 
 /* Which kernels the streaming forward and backward WOULD launch for a shape
  * (host only: no launch, no device access), so a test can assert that a case
- * reaches the dispatch class it was written for.  Computed by the predicates
- * the dispatch itself calls.  CG_ERR_UNSUPPORTED when the forward or the
+ * reaches the dispatch class it was written for.  A read-out of the route the
+ * forward and the backward themselves act on.  CG_ERR_UNSUPPORTED when the forward or the
  * backward of the shape is not on the streaming path, or `layout` (CG_BASIS_*)
  * does not apply.  out[CG_SD_*]; a field that does not apply is 0
  * (CG_SD_LAST_STAGED: -1). */
