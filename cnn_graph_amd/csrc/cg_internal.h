@@ -24,7 +24,7 @@ __host__ __device__ inline size_t align16(size_t b) { return (b + 15) & ~size_t(
 // Kernel-selection options (cg_set_option, CG_OPT_* in include/cheb_mi355.h):
 // process-wide, read by the launch code at every launch
 enum Opt { kOptDwDirect = 0, kOptDwW2, kOptDwWaves, kOptSpmmPw, kOptGrp16, kOptGrpPc, kOptClenDy,
-           kOptSeqXpre, kOptDwX3, kOptGemmX3, kOptCount };
+           kOptSeqXpre, kOptDwX3, kOptGemmX3, kOptMfmaStagger, kOptCount };
 int option(Opt o);
 
 // Timing-ablation switches (bits 0-7 forward resident kernel, 8-15 backward,
@@ -238,6 +238,7 @@ struct FastBwdArgs {
   int bord;            // basis layout, as FastFwdArgs::bord
   unsigned long long* ts;  // ablation build: phase timestamps (CG_TS), else NULL
   int x3;              // dBasis = dy W^T on the split-bf16 matrix pipe (CG_OPT_GEMM_X3)
+  int stg;             // CG_OPT_MFMA_STAGGER: 0, or the wave-class map (1: wave & 3, 2: wave >> 2)
 };
 hipError_t launch_fast_forward(const FastGeom& g, int N, const FastFwdArgs& a, hipStream_t s);
 hipError_t launch_fast_backward(const FastGeom& g, int N, const FastBwdArgs& a, hipStream_t s);

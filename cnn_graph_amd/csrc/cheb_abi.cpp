@@ -564,7 +564,7 @@ void stream_dispatch(const ChebRoute& r, int32_t* out) {
 namespace cg {
 namespace {
 // CG_OPT_* values (defaults: the measured-faster kernels) and their ranges
-std::atomic<int> g_opts[kOptCount] = {{1}, {1}, {8}, {1}, {1}, {1}, {1}, {1}, {1}, {1}};
+std::atomic<int> g_opts[kOptCount] = {{1}, {1}, {8}, {1}, {1}, {1}, {1}, {1}, {1}, {1}, {2}};
 // The release library accepts only the values a user would choose between;
 // the alternatives that lost every A/B exist in the ablation
 // build only (`make debug`): CG_OPT_DW_DIRECT 2 / 3 (forced direct dW), CG_OPT_DW_W2
@@ -585,6 +585,7 @@ bool option_valid(int o, int v) {
     case kOptDwWaves: return v == 4 || v == 8;
     case kOptClenDy: return v >= 0 && v <= 2;
     case kOptSeqXpre: return v >= 0 && v <= 2;
+    case kOptMfmaStagger: return v >= 0 && v <= 2;
     default: return v == 0 || v == 1;
   }
 }
@@ -1027,6 +1028,7 @@ int backward_impl(cg_plan* plan, int32_t N, int32_t Fin, int32_t K, int32_t Fout
                           dx_acc, r.fast.dscratch, plan->tfast.view, dy, basis, W, dx,
                           fused ? slabs : nullptr, layout == CG_BASIS_ORDERS ? basis_mb(M) : 0};
         a.x3 = cg::option(cg::kOptGemmX3) != 0 ? 1 : 0;
+        a.stg = cg::option(cg::kOptMfmaStagger);
 #ifdef CG_DEBUG
         a.ts = cg::g_debug_ts;
 #endif

@@ -543,6 +543,19 @@ struct Bwd {
   // consumed every 6 recurrence steps (BUF == 5)
   float xr[8], yr[8];
   int ngrp, oct_lim;
+  // CG_OPT_MFMA_STAGGER (kStg: Fin = 1; the Fin = 2 build is out of registers
+  // and spills more with any change here).  A workgroup puts four waves on
+  // each SIMD, which share its one matrix pipe.  The X3 recurrence repeats
+  // with the ring's period, 3 steps, and a group runs in every second visit
+  // of the step i = 2 (mod 3); bpar (wave-uniform) counts the visits mod 2.
+  // Unstaggered every wave starts at bpar = 0 (groups at i = 5, 11, ...);
+  // staggered, the waves of even class start at 1 (i = 2, 8, ...), so two of a
+  // SIMD's four waves carry a group in one step and two in another.  The
+  // class tells a wave from the others on its SIMD (stg 1: wave & 3, 2:
+  // wave >> 2).  gdone: groups run so far (they keep their order: dacc's
+  // operation sequence does not depend on the schedule)
+  static constexpr bool kStg = X3 && FV == 1;
+  int bpar, gdone;
 
   __device__ __forceinline__ Bwd(const FastBwdArgs& a, char* smem, int tid) : A(a) {
     K = a.K;
@@ -680,7 +693,16 @@ struct Bwd {
     V gth[L > 0 ? L : 1];
     if (i >= 1) r.template gather<FV, L, NX1>(ring, gth);
     // (ablation build: bit 64 skips the dW MFMAs, bit 128 the dW loads)
-    if constexpr (X3) {
+    if constexpr (kStg) {
+      if (BUF == 5) {  // (run() gives BUF 5 to every step i = 2 (mod 3))
+        bpar ^= 1;
+        if (bpar == 0 && gdone < ngrp) {  // one group's MFMAs, the next group's loads
+          dw_x3_mfma(gdone);
+          if (gdone + 1 < ngrp) dw_x3_load(gdone + 1);
+          ++gdone;
+        }
+      }
+    } else if constexpr (X3) {
       if (BUF == 5 && i / 6 < ngrp) {  // every sixth step: one group's MFMAs, the next group's loads
         dw_x3_mfma(i / 6);
         if (i / 6 + 1 < ngrp) dw_x3_load(i / 6 + 1);
@@ -736,6 +758,11 @@ struct Bwd {
       const int no = oct_lim > wave ? (oct_lim - wave + kW - 1) / kW : 0;  // this wave's octets
       ngrp = (no + 1) >> 1;
       npair = 0;
+      if (kStg) {
+        const int cls = A.stg == 1 ? (wave & 3) : (wave >> 2);
+        bpar = (A.stg != 0 && (cls & 1) == 0) ? 1 : 0;
+        gdone = 0;
+      }
 #pragma unroll
       for (int e = 0; e < 16; ++e) dacc[e] = 0.f;
       if (ngrp > 0) dw_x3_load(0);
@@ -769,6 +796,14 @@ struct Bwd {
   template <int L>
   __device__ __forceinline__ void run() {
     static_assert(PF == 6, "the loop below cycles the ring (3) and the dW buffers (6)");
+    if constexpr (kStg) {  // no dW buffers to cycle: the ring's period, half the code
+      for (int i = 0; i < K; i += 3) {
+        step<L, 0, 2, 1, 0>(i);
+        if (i + 1 < K) step<L, 1, 0, 2, 1>(i + 1);
+        if (i + 2 < K) step<L, 2, 1, 0, 5>(i + 2);
+      }
+      return;
+    }
     for (int i = 0; i < K; i += 6) {
       step<L, 0, 2, 1, 0>(i);
       if (i + 1 < K) step<L, 1, 0, 2, 1>(i + 1);
@@ -940,8 +975,10 @@ __global__ __launch_bounds__(kT) void cheb_bwd_fast(FastBwdArgs A) {
   if (DW) {
     // remaining row pairs / groups (K small relative to M/32), then the cross-wave sum
     if constexpr (B::X3) {
-      for (int g = c.K / 6; g < c.ngrp; ++g) {
-        // (group K / 6 was loaded by the last in-loop group, or by go())
+      for (int g = B::kStg ? c.gdone : c.K / 6; g < c.ngrp; ++g) {
+        // (from the first group the wave did not reach in the loop -- with the
+        // stagger that depends on its class; it was loaded by the last in-loop
+        // group, or by go())
         c.dw_x3_mfma(g);
         if (g + 1 < c.ngrp) c.dw_x3_load(g + 1);
       }

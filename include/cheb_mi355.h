@@ -103,7 +103,15 @@ enum {
                            GEMMs (y = basis W, dBasis = dy W^T) and the gconv-LSTM BPTT
                            step's D_k = dpre Wh_k^T (f32-accurate; not bitwise the f32
                            kernels) (default); 0: f32 MFMA                            */
-  CG_OPT_COUNT = 10
+  CG_OPT_MFMA_STAGGER = 10, /* the fast backward's fused-dW groups (Fin = 1 with
+                           CG_OPT_GEMM_X3 = 1: config B) run three recurrence steps
+                           earlier in two of a SIMD's four waves, so its waves do not
+                           all queue their matrix work inside one barrier-delimited
+                           step; the waves are told apart by 2: wave >> 2 (default),
+                           1: wave & 3; 0: every wave in the same step.  Every value
+                           gives the same bits (a wave's own operation order is
+                           unchanged)                                                 */
+  CG_OPT_COUNT = 11
 };
 
 typedef struct cg_plan cg_plan;
