@@ -119,6 +119,11 @@ _SIGNATURES = {
                          _vp, _c_sz, _vp], _c_int),
     "cg_fres_backward": ([_c_i32, _c_i32, _c_i32, _c_i32, _vp, _c_sz, _vp, _vp, _vp, _vp, _c_i32,
                           _vp, _vp, _c_i32, _vp, _vp, _c_sz, _vp], _c_int),
+    "cg_fres_forward_drop": ([_c_i32, _c_i32, _c_i32, _c_i32, _vp, _c_sz, _vp, _vp, ctypes.c_float,
+                              ctypes.c_uint64, _vp, _c_i32, _vp, _vp, _vp, _c_sz, _vp], _c_int),
+    "cg_fres_backward_drop": ([_c_i32, _c_i32, _c_i32, _c_i32, _vp, _c_sz, _vp, _vp, _vp, _vp, _c_i32,
+                               ctypes.c_float, ctypes.c_uint64, _vp, _vp, _vp, _vp, _c_sz, _vp],
+                              _c_int),
     "cg_lstm_cell_forward": ([_c_i64, _c_i32, _c_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
                              _c_int),
     "cg_lstm_cell_backward": ([_c_i64, _c_i32, _c_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],

@@ -542,6 +542,13 @@ struct GftEx {
 };
 hipError_t launch_gft_ex(const void* basis, int inverse, int N, int M, int C, const float* in,
                          float* out, bool x3, const GftEx& e, hipStream_t s);
+// The LSTM -> head seam (cg_fres_*_drop): the DropoutWrapper's mask folded into
+// the transform.  Analysis (inverse 0): the operand is staged as
+// drop_one(in[e], keep, seed, e, 0), e the element's flat index in [N][M][C] --
+// the value k_dropout would have written.  Synthesis (inverse 1): the store is
+// out[e] = drop_one(acc, keep, seed, e, 1), the dropout's backward form.
+hipError_t launch_gft_drop(const void* basis, int inverse, int N, int M, int C, const float* in,
+                           float* out, bool x3, float keep, unsigned long long seed, hipStream_t s);
 // per-frequency contraction (forms of cg_fourier_mix)
 hipError_t launch_fmix(int form, int64_t R, int M, int Cin, int Cout, const float* W, const float* x,
                        const float* g, const float* add, float* out, hipStream_t s);
@@ -562,6 +569,26 @@ hipError_t launch_rmsprop(float* param, const float* grad, float* ms, float* mom
                           float rho, float momentum, float eps, float grad_scale, hipStream_t s);
 hipError_t launch_adam(float* param, const float* grad, float* m, float* v, int64_t n, float lr_t,
                        float beta1, float beta2, float eps, float grad_scale, hipStream_t s);
+// tf.nn.dropout's mask draw, the single definition k_dropout / k_dropout4 and
+// k_gft's dropout modes share, so all agree bitwise.
+// U[0, 1) of element i under `seed` (splitmix64 finaliser of a Weyl sequence;
+// 24 random bits, so u + keep rounds like tf.random_uniform's fp32 draw)
+__device__ __forceinline__ float drop_u(unsigned long long seed, int64_t i) {
+  unsigned long long z = seed + 0x9E3779B97F4A7C15ull * (static_cast<unsigned long long>(i) + 1ull);
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return float(z >> 40) * (1.f / 16777216.f);
+}
+
+// bwd = 0: y = (x / keep) * floor(keep + u);  bwd = 1: y = (x * floor(keep + u)) / keep
+__device__ __forceinline__ float drop_one(float x, float keep, unsigned long long seed, int64_t i,
+                                          int bwd) {
+#pragma clang fp contract(off)
+  const float b = floorf(keep + drop_u(seed, i));
+  return bwd ? (x * b) / keep : (x / keep) * b;
+}
+
 // One Adam step applied by the slab reduction that produces its gradient.
 struct AdamStep {
   float* param;

@@ -1766,6 +1766,72 @@ int cg_fres_backward(int32_t N, int32_t M, int32_t Fin, int32_t Fout, const void
   return ok();
 }
 
+// ---- the LSTM -> head seam: the DropoutWrapper's mask inside the transforms --------
+static int check_keep(const char* what, float keep_prob) {
+  if (!(keep_prob > 0.f && keep_prob <= 1.f))
+    return fail(CG_ERR_ARG, "%s: keep_prob must be in (0, 1], got %g", what, double(keep_prob));
+  return CG_OK;
+}
+
+int cg_fres_forward_drop(int32_t N, int32_t M, int32_t Fin, int32_t Fout, const void* basis,
+                         size_t basis_bytes, const float* W, const float* x, float keep_prob,
+                         uint64_t seed, const float* residual, int32_t act, float* xhat, float* y,
+                         void* workspace, size_t ws_bytes, void* stream) {
+  int rc = check_keep("fres_forward_drop", keep_prob);
+  if (rc) return rc;
+  if (keep_prob == 1.f)  // the identity: the plain call's launches, so its bits
+    return cg_fres_forward(N, M, Fin, Fout, basis, basis_bytes, W, x, residual, act, xhat, y,
+                           workspace, ws_bytes, stream);
+  rc = check_fres("fres_forward_drop", N, M, Fin, Fout, basis, basis_bytes);
+  if (rc) return rc;
+  if (!W || !x || !xhat || !y) return fail(CG_ERR_ARG, "fres_forward_drop: null W / x / xhat / y");
+  if (act != CG_ACT_NONE && act != CG_ACT_RELU)
+    return fail(CG_ERR_ARG, "fres_forward_drop: act must be CG_ACT_NONE or CG_ACT_RELU, got %d", act);
+  const size_t need = al256(size_t(N) * M * Fout * 4);
+  if (!workspace || ws_bytes < need)
+    return fail(CG_ERR_ARG, "fres_forward_drop workspace too small: %zu < %zu", ws_bytes, need);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const bool x3 = cg::option(cg::kOptGemmX3) != 0;
+  float* yhat = static_cast<float*>(workspace);
+  CG_HIP(cg::launch_gft_drop(basis, 0, N, M, Fin, x, xhat, x3, keep_prob, seed, s));
+  CG_HIP(cg::launch_fmix(0, N, M, Fin, Fout, W, xhat, nullptr, nullptr, yhat, s));
+  const cg::GftEx e{nullptr, nullptr, residual, act == CG_ACT_RELU, 0};
+  CG_HIP(cg::launch_gft_ex(basis, 1, N, M, Fout, yhat, y, x3, e, s));
+  return ok();
+}
+
+int cg_fres_backward_drop(int32_t N, int32_t M, int32_t Fin, int32_t Fout, const void* basis,
+                          size_t basis_bytes, const float* W, const float* xhat, const float* dy,
+                          const float* y, int32_t act, float keep_prob, uint64_t seed, float* dz,
+                          float* dx, float* dW, void* workspace, size_t ws_bytes, void* stream) {
+  int rc = check_keep("fres_backward_drop", keep_prob);
+  if (rc) return rc;
+  if (!dx) return fail(CG_ERR_ARG, "fres_backward_drop: dx is required");
+  if (keep_prob == 1.f)
+    return cg_fres_backward(N, M, Fin, Fout, basis, basis_bytes, W, xhat, dy, y, act, dz, dx, 0, dW,
+                            workspace, ws_bytes, stream);
+  rc = check_fres("fres_backward_drop", N, M, Fin, Fout, basis, basis_bytes);
+  if (rc) return rc;
+  if (!W || !xhat || !dy || !dW)
+    return fail(CG_ERR_ARG, "fres_backward_drop: null W / xhat / dy / dW");
+  if (act != CG_ACT_NONE && act != CG_ACT_RELU)
+    return fail(CG_ERR_ARG, "fres_backward_drop: act must be CG_ACT_NONE or CG_ACT_RELU, got %d", act);
+  if (act == CG_ACT_RELU && !y) return fail(CG_ERR_ARG, "fres_backward_drop: act relu needs y");
+  const size_t yout = al256(size_t(N) * M * Fout * 4), xin = al256(size_t(N) * M * Fin * 4);
+  if (!workspace || ws_bytes < yout + xin)
+    return fail(CG_ERR_ARG, "fres_backward_drop workspace too small: %zu < %zu", ws_bytes, yout + xin);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const bool x3 = cg::option(cg::kOptGemmX3) != 0;
+  float* ghat = static_cast<float*>(workspace);
+  float* dxhat = reinterpret_cast<float*>(static_cast<char*>(workspace) + yout);
+  const cg::GftEx mask{act == CG_ACT_RELU ? y : nullptr, dz, nullptr, 0, 0};
+  CG_HIP(cg::launch_gft_ex(basis, 0, N, M, Fout, dy, ghat, x3, mask, s));
+  CG_HIP(cg::launch_fmix(2, N, M, Fin, Fout, nullptr, xhat, ghat, nullptr, dW, s));
+  CG_HIP(cg::launch_fmix(1, N, M, Fin, Fout, W, nullptr, ghat, nullptr, dxhat, s));
+  CG_HIP(cg::launch_gft_drop(basis, 1, N, M, Fin, dxhat, dx, x3, keep_prob, seed, s));
+  return ok();
+}
+
 static int check_lstm(int64_t R, int32_t H, int32_t gates) {
   if (R < 1 || H < 1) return fail(CG_ERR_ARG, "lstm: bad shape R=%lld H=%d", (long long)R, H);
   if (R * int64_t(H) * 4 >= (int64_t(1) << 31))

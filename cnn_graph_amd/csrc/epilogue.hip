@@ -44,24 +44,7 @@ __global__ __launch_bounds__(256) void k_act_fwd(float* __restrict__ y, const fl
   }
 }
 
-// U[0, 1) of element i under `seed` (splitmix64 finaliser of a Weyl sequence;
-// 24 random bits, so u + keep rounds like tf.random_uniform's fp32 draw)
-__device__ __forceinline__ float drop_u(unsigned long long seed, int64_t i) {
-  unsigned long long z = seed + 0x9E3779B97F4A7C15ull * (static_cast<unsigned long long>(i) + 1ull);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return float(z >> 40) * (1.f / 16777216.f);
-}
-
-// bwd = 0: y = (x / keep) * floor(keep + u);  bwd = 1: y = (x * floor(keep + u)) / keep
-__device__ __forceinline__ float drop_one(float x, float keep, unsigned long long seed, int64_t i,
-                                          int bwd) {
-#pragma clang fp contract(off)
-  const float b = floorf(keep + drop_u(seed, i));
-  return bwd ? (x * b) / keep : (x / keep) * b;
-}
-
+// drop_u / drop_one: cg_internal.h (shared with k_gft's dropout modes)
 __global__ __launch_bounds__(256) void k_dropout(const float* __restrict__ x, float* __restrict__ y,
                                                  int64_t n, float keep, unsigned long long seed,
                                                  int bwd) {

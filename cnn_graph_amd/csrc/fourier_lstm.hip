@@ -33,6 +33,11 @@
 //              as in * [mask_y > 0] (the ReLU backward, kept in dz by the first
 //              row block of each column tile), and the store is
 //              out = act(acc + residual) or out += acc.
+//              DR (the LSTM -> head seam, cg_fres_*_drop; a template parameter,
+//              so the other instantiations are unchanged): DR = 1 stages the
+//              operand as drop_one(in[e], keep, seed, e, 0), DR = 2 stores
+//              drop_one(acc, keep, seed, e, 1); e is the flat [N][M][C] index
+//              both already form as their load / store address.
 //   k_fmix     the per-frequency contraction, one wave per (m, 32 x 32 tile)
 //              on v_mfma_f32_32x32x2_f32 with strided operands: forward,
 //              transposed and weight-gradient forms are the same kernel with
@@ -68,6 +73,9 @@ struct GftArgs {
   float* dz;            // receives the staged operand; NULL = not kept
   const float* res;     // out = act(acc + res); NULL = 0
   int relu, accum;      // accum: out += acc
+  // DR only
+  float keep;
+  unsigned long long seed;
 };
 
 // element offset of row 0 of column jj of column tile bx (row stride C); false = padding
@@ -85,7 +93,7 @@ __device__ __forceinline__ bool gft_col(const GftArgs& a, int bx, int jj, int64_
   return j < int64_t(a.N) * a.C;
 }
 
-template <bool X3, bool EX>
+template <bool X3, bool EX, int DR = 0>
 __global__ __launch_bounds__(256) void k_gft(GftArgs a) {
 #pragma clang fp contract(off)
   // X3: 2 buffers x 3 terms x 128 columns x 48 B (16 k as bf16 + 16 B of padding:
@@ -136,6 +144,14 @@ __global__ __launch_bounds__(256) void k_gft(GftArgs a) {
         for (int q = 0; q < 8; ++q)
           if (k0 + q < a.M) a.dz[soff + int64_t(k0 + q) * a.C] = v[q];
       }
+    }
+    if constexpr (DR == 1) {
+      // the mask where the loads are consumed (as EX's); a padding element is 0
+      // and stays 0, its index addresses nothing
+      const int k0 = ks * 16 + sh * 8;
+#pragma unroll
+      for (int q = 0; q < 8; ++q)
+        v[q] = drop_one(v[q], a.keep, a.seed, soff + int64_t(k0 + q) * a.C, 0);
     }
     if constexpr (X3) {
       bf16x8* L = reinterpret_cast<bf16x8*>(smem) + buf * (3 * 128 * 3);
@@ -207,6 +223,7 @@ __global__ __launch_bounds__(256) void k_gft(GftArgs a) {
             if (a.relu) val = val > 0.f ? val : 0.f;
             if (a.accum) val = a.out[e] + val;
           }
+          if constexpr (DR == 2) val = drop_one(val, a.keep, a.seed, e, 1);
           a.out[e] = val;
         }
     }
@@ -400,6 +417,33 @@ static hipError_t launch_gft_any(const void* basis, int inverse, int N, int M, i
     hipLaunchKernelGGL((k_gft<true, false>), grid, dim3(256), 0, s, a);
   } else {
     hipLaunchKernelGGL((k_gft<false, false>), grid, dim3(256), 0, s, a);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_gft_drop(const void* basis, int inverse, int N, int M, int C, const float* in,
+                           float* out, bool x3, float keep, unsigned long long seed, hipStream_t s) {
+  GftArgs a{};
+  const size_t Mp = size_t(gft_pad(M));
+  const char* b = static_cast<const char*>(basis);
+  a.A = x3 ? b + size_t(inverse ? 1 : 0) * 3 * Mp * Mp * 2
+           : b + 6 * Mp * Mp * 2 + size_t(inverse ? 1 : 0) * Mp * Mp * 4;
+  a.in = in;
+  a.out = out;
+  a.M = M, a.Mp = int(Mp), a.C = C, a.N = N;
+  a.keep = keep, a.seed = seed;
+  const int64_t ctiles = (int64_t(N) * C + kGftTile - 1) / kGftTile;
+  if (ctiles > 2147483647) return hipErrorInvalidValue;
+  const dim3 grid(unsigned(ctiles), unsigned(Mp / kGftTile));
+  if (inverse) {
+    if (x3)
+      hipLaunchKernelGGL((k_gft<true, false, 2>), grid, dim3(256), 0, s, a);
+    else
+      hipLaunchKernelGGL((k_gft<false, false, 2>), grid, dim3(256), 0, s, a);
+  } else if (x3) {
+    hipLaunchKernelGGL((k_gft<true, false, 1>), grid, dim3(256), 0, s, a);
+  } else {
+    hipLaunchKernelGGL((k_gft<false, false, 1>), grid, dim3(256), 0, s, a);
   }
   return hipGetLastError();
 }

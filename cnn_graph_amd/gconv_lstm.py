@@ -907,28 +907,64 @@ class GLSTMModel:
                   self.loss.data_ptr(), self.dout.data_ptr(), self.ema.data_ptr(),
                   ctypes.c_float(0.9), self.mws.data_ptr(), self.mws_n, s)
         out.backward(self.dout)
-        for p in self.params:  # autograd accumulated into the flat bucket in place
-            if p.grad is None or p.grad.data_ptr() < self.grad.data_ptr() or \
-                    p.grad.data_ptr() >= self.grad.data_ptr() + 4 * self.grad.numel():
-                raise RuntimeError("a parameter's .grad left the flat gradient bucket")
-        world = 1
-        if self.comm is not None and self.comm.world > 1:
-            self.comm.allreduce_sum_(self.grad, s)
-            world = self.comm.world
-        self.step_count += 1
-        lr = self.learning_rate(self.step_count - 1)
-        n = self.flat.numel()
-        if self.optimizer == "adam":
-            _lib.call("cg_adam_update", self.flat.data_ptr(), self.grad.data_ptr(), self.s1.data_ptr(),
-                      self.s2.data_ptr(), n, ctypes.c_float(lr), ctypes.c_float(0.9),
-                      ctypes.c_float(0.999), ctypes.c_float(1e-8), self.step_count,
-                      ctypes.c_float(1.0 / world), s)
-        elif self.optimizer == "sgd":
-            _lib.call("cg_sgd_update", self.flat.data_ptr(), self.grad.data_ptr(), n,
-                      ctypes.c_float(lr), ctypes.c_float(1.0 / world), s)
-        else:
-            _lib.call("cg_rmsprop_update", self.flat.data_ptr(), self.grad.data_ptr(),
-                      self.s1.data_ptr(), self.s2.data_ptr(), n, ctypes.c_float(lr),
-                      ctypes.c_float(0.9), ctypes.c_float(0.0), ctypes.c_float(1e-10),
-                      ctypes.c_float(1.0 / world), s)
+        _exchange_and_update(self, s)
         return self.loss
+
+    def predict(self, data, labels=None, reference_dropout: bool = False):
+        """GraphModel.predict (lib/graph_model.py:64-94; evaluate.predict has the
+        padding and the ``loss * batch_size / size`` quirk): data [size, M, F*T]
+        -> predictions [size, M, out_features], with labels also the loss.
+
+        Dropout at evaluation: the reference's DropoutWrapper(0.8) inside
+        glstm_layer is a constant of the graph, so the reference ALSO drops
+        when it evaluates.  Here the default is no dropout (deterministic
+        predictions); ``reference_dropout=True`` applies the wrappers' masks as
+        a training forward does (and advances their mask streams)."""
+        from . import evaluate as _ev
+
+        def fwd(batch):
+            wrapped = self.wrapped
+            if not reference_dropout:
+                self.wrapped = self.cells
+            try:
+                return self.forward(batch)
+            finally:
+                self.wrapped = wrapped
+
+        return _ev.predict(fwd, self.N, self.device, data, labels)
+
+    def evaluate(self, data, labels, reference_dropout: bool = False):
+        """GraphModel.evaluate (lib/graph_model.py:96-122):
+        (string, mse, 0, loss, predictions)."""
+        from . import evaluate as _ev
+        return _ev.evaluate(lambda d, l: self.predict(d, l, reference_dropout), data, labels)
+
+
+def _exchange_and_update(m, s):
+    """The tail of a flat-bucket training step (GLSTMModel, GLSTMGconvModel):
+    every .grad still inside the bucket, ONE all-reduce when world > 1, ONE
+    optimizer launch with grad_scale = 1/world."""
+    for p in m.params:  # autograd accumulated into the flat bucket in place
+        if p.grad is None or p.grad.data_ptr() < m.grad.data_ptr() or \
+                p.grad.data_ptr() >= m.grad.data_ptr() + 4 * m.grad.numel():
+            raise RuntimeError("a parameter's .grad left the flat gradient bucket")
+    world = 1
+    if m.comm is not None and m.comm.world > 1:
+        m.comm.allreduce_sum_(m.grad, s)
+        world = m.comm.world
+    m.step_count += 1
+    lr = m.learning_rate(m.step_count - 1)
+    n = m.flat.numel()
+    if m.optimizer == "adam":
+        _lib.call("cg_adam_update", m.flat.data_ptr(), m.grad.data_ptr(), m.s1.data_ptr(),
+                  m.s2.data_ptr(), n, ctypes.c_float(lr), ctypes.c_float(0.9),
+                  ctypes.c_float(0.999), ctypes.c_float(1e-8), m.step_count,
+                  ctypes.c_float(1.0 / world), s)
+    elif m.optimizer == "sgd":
+        _lib.call("cg_sgd_update", m.flat.data_ptr(), m.grad.data_ptr(), n,
+                  ctypes.c_float(lr), ctypes.c_float(1.0 / world), s)
+    else:
+        _lib.call("cg_rmsprop_update", m.flat.data_ptr(), m.grad.data_ptr(),
+                  m.s1.data_ptr(), m.s2.data_ptr(), n, ctypes.c_float(lr),
+                  ctypes.c_float(0.9), ctypes.c_float(0.0), ctypes.c_float(1e-10),
+                  ctypes.c_float(1.0 / world), s)

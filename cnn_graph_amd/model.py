@@ -56,9 +56,15 @@ from .plan import plan_for
 class _ResNet:
     """One ``residual_network`` (lib/graph_conv.py:305-330): conv_init, R
     residual layers of two filters each, convN.  Its weights and gradients are
-    views into the owner's flat buffers starting at ``off``."""
+    views into the owner's flat buffers starting at ``off``.
 
-    def __init__(self, owner, scope: str, Fin: int, off: int, gen):
+    ``input_grad``: the input is an activation, not data (the network sits
+    behind an LSTM, lib/gconv_lstm.py:382-389): conv_init's backward also
+    computes dx into ``dx_in`` [N, M, Fin].  ``names`` replaces the variable
+    names (same order)."""
+
+    def __init__(self, owner, scope: str, Fin: int, off: int, gen, input_grad: bool = False,
+                 names=None):
         self.o = owner
         N, M, K, F = owner.N, owner.M, owner.K, owner.nfilter
         # (scope, Fin, Fout, act) in the reference's call order
@@ -79,7 +85,7 @@ class _ResNet:
             self.dW.append(owner.grad[off:off + sz].view(fi * K, fo))
             off += sz
         self.end = off
-        self.names = [name for name, *_ in layers]
+        self._finish(names, input_grad, f32)
         # activations / bases saved by the forward, gradient work buffers; the
         # basis layout per filter: planes where it applies, else rows
         self.layout = ["planes" if owner.plan.basis_elems(N, fi, K, fo, "planes") else "rows"
@@ -88,6 +94,13 @@ class _ResNet:
                       for (_, fi, _, _), lay in zip(layers, self.layout)]
         self.out = [torch.empty((N, M, fo), **f32) for _, _, fo, _ in layers]
         self.g = [torch.empty((N, M, F), **f32) for _ in range(3)]
+
+    def _finish(self, names, input_grad, f32):
+        self.names = list(names) if names is not None else [name for name, *_ in self.layers]
+        if len(self.names) != len(self.layers):
+            raise ValueError(f"{len(self.layers)} filters, {len(self.names)} names")
+        self.input_grad = bool(input_grad)
+        self.dx_in = torch.empty((self.o.N, self.o.M, self.Fin), **f32) if input_grad else None
 
     @staticmethod
     def sizes(Fin, F, K, R, Fout_last):
@@ -129,7 +142,8 @@ class _ResNet:
         return self._f(li, h, None, s)
 
     def backward(self, dout, s):
-        """Every dW of this network from d(out); the input gets no gradient (data)."""
+        """Every dW of this network from d(out); the input gets no gradient (data)
+        unless ``input_grad``: then ``dx_in`` receives it."""
         last = len(self.layers) - 1
         bufs = self.g
         dh = bufs[0]
@@ -143,15 +157,23 @@ class _ResNet:
             self._b(li, dt, dh, dz1, True, s)              # sublayer0: dz1 += dx  (dh buffer as dz0)
             dh, cur = dz1, (cur + 1) % 3
             li -= 2
-        self._b(0, dh, bufs[(cur + 1) % 3], None, False, s)  # conv_init (no dx: x is data)
+        # conv_init (no dx when x is data)
+        self._b(0, dh, bufs[(cur + 1) % 3], self.dx_in, False, s)
 
 
 class _FourierResNet(_ResNet):
     """The same network with the Fourier filter: _ResNet's forward / backward
     schedule over cg_fres_forward / cg_fres_backward.  Weights [M, Fout, Fin]
-    (lib/graph_conv.py:105); the forward saves each filter's spectrum xhat."""
+    (lib/graph_conv.py:105); the forward saves each filter's spectrum xhat.
 
-    def __init__(self, owner, scope: str, Fin: int, off: int, gen):
+    ``drop`` = (keep_prob, seed) or None: conv_init reads its input through a
+    dropout mask folded into the transforms (cg_fres_forward_drop /
+    cg_fres_backward_drop; needs ``input_grad``)."""
+
+    drop = None
+
+    def __init__(self, owner, scope: str, Fin: int, off: int, gen, input_grad: bool = False,
+                 names=None):
         self.o = owner
         N, M, F = owner.N, owner.M, owner.nfilter
         layers = [(f"{scope}conv_init/weights", Fin, F, "relu")]
@@ -171,7 +193,7 @@ class _FourierResNet(_ResNet):
             self.dW.append(owner.grad[off:off + sz].view(M, fo, fi))
             off += sz
         self.end = off
-        self.names = [name for name, *_ in layers]
+        self._finish(names, input_grad, f32)
         self.xhat = [torch.empty((N, M, fi), **f32) for _, fi, _, _ in layers]
         self.out = [torch.empty((N, M, fo), **f32) for _, _, fo, _ in layers]
         self.g = [torch.empty((N, M, F), **f32) for _ in range(3)]
@@ -187,6 +209,14 @@ class _FourierResNet(_ResNet):
     def _f(self, li, x, res, s):
         o = self.o
         _, fi, fo, act = self.layers[li]
+        if li == 0 and self.drop is not None:
+            keep, seed = self.drop
+            st = _lib.lib().cg_fres_forward_drop(
+                o.N, o.M, fi, fo, o.gft.data_ptr(), o.gft.numel(), self.W[li].data_ptr(), x.data_ptr(),
+                ctypes.c_float(keep), seed, None, ops.ACTS[act], self.xhat[li].data_ptr(),
+                self.out[li].data_ptr(), o.ws.data_ptr(), o.ws_n, s)
+            _lib.check("cg_fres_forward_drop", st)
+            return self.out[li]
         st = o._fwd(o.N, o.M, fi, fo, o.gft.data_ptr(), o.gft.numel(), self.W[li].data_ptr(),
                     x.data_ptr(), res.data_ptr() if res is not None else None, ops.ACTS[act],
                     self.xhat[li].data_ptr(), self.out[li].data_ptr(), o.ws.data_ptr(), o.ws_n, s)
@@ -196,6 +226,16 @@ class _FourierResNet(_ResNet):
     def _b(self, li, dy, dz, dx, dx_acc, s):
         o = self.o
         _, fi, fo, act = self.layers[li]
+        if li == 0 and self.drop is not None:
+            keep, seed = self.drop
+            st = _lib.lib().cg_fres_backward_drop(
+                o.N, o.M, fi, fo, o.gft.data_ptr(), o.gft.numel(), self.W[li].data_ptr(),
+                self.xhat[li].data_ptr(), dy.data_ptr(), self.out[li].data_ptr(), ops.ACTS[act],
+                ctypes.c_float(keep), seed, dz.data_ptr() if dz is not None else None,
+                dx.data_ptr() if dx is not None else None, self.dW[li].data_ptr(), o.ws.data_ptr(),
+                o.ws_n, s)
+            _lib.check("cg_fres_backward_drop", st)
+            return
         st = o._bwd(o.N, o.M, fi, fo, o.gft.data_ptr(), o.gft.numel(), self.W[li].data_ptr(),
                     self.xhat[li].data_ptr(), dy.data_ptr(), self.out[li].data_ptr(), ops.ACTS[act],
                     dz.data_ptr() if dz is not None else None,
@@ -299,6 +339,19 @@ class _Trainer:
 
     def _stream(self, stream):
         return stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream
+
+    def predict(self, data, labels=None):
+        """GraphModel.predict (lib/graph_model.py:64-94): predictions [size, M,
+        Fout_last] over batches of N, the last one zero-padded; with labels also
+        the reference's ``loss * batch_size / size`` (evaluate.predict has the
+        quirk).  No parameter, Adam slot, loss average or step count changes."""
+        from . import evaluate as _ev
+        return _ev.predict(self.forward, self.N, self.device, data, labels)
+
+    def evaluate(self, data, labels):
+        """GraphModel.evaluate (:96-122): (string, mse, 0, loss, predictions)."""
+        from . import evaluate as _ev
+        return _ev.evaluate(self.predict, data, labels)
 
     def parameters(self):
         return dict(zip(self.names, self.W))

@@ -835,7 +835,7 @@ class _Dropout(torch.autograd.Function):
         return dx, None, None
 
 
-DROP_WEYL = 0x9E3779B97F4A7C15  # the mask draw's Weyl increment (epilogue.hip drop_u)
+DROP_WEYL = 0x9E3779B97F4A7C15  # the mask draw's Weyl increment (cg_internal.h drop_u)
 
 
 def dropout(x, keep_prob: float, seed: int, offset: int = 0):
@@ -1182,6 +1182,78 @@ def fres_backward(basis, W, xhat, dy, y=None, act: str = "none", need_dz: bool =
     _lib.call("cg_fres_backward", N, M, Fin, Fout, _p(basis), basis.numel(), _p(W), _p(xhat), _p(dy),
               _p(y) if act == "relu" else None, ACTS[act], _p(dz), _p(dx), int(dx_accumulate),
               _p(dW), _p(ws), bb, _stream(dy))
+    return dx, dW, dz
+
+
+def _check_keep(keep_prob):
+    if not 0.0 < float(keep_prob) <= 1.0:
+        raise ValueError(f"keep_prob must be in (0, 1], got {keep_prob}")
+
+
+def fres_forward_drop(basis, W, x, keep_prob: float, seed: int, residual=None, act: str = "none",
+                      out_xhat=None, out_y=None, ws=None):
+    """fres_forward of dropout(x, keep_prob, seed) without the dropped tensor
+    (cg_fres_forward_drop): the mask is applied while the analysis stages x --
+    bit for bit ``dropout`` then ``fres_forward``.  ``seed`` already carries a
+    slice offset (``dropout``'s folding: seed + DROP_WEYL * offset).  Returns
+    (xhat of the dropped x [N, M, Fin], y [N, M, Fout])."""
+    _check_keep(keep_prob)
+    for name, t in (("x", x), ("W", W)):
+        _check_dev(name, t)
+    x, W = x.contiguous(), W.contiguous()
+    N, M, Fin = (int(s) for s in x.shape)
+    if W.dim() != 3 or tuple(W.shape[::2]) != (M, Fin):
+        raise ValueError(f"W must be [M, Fout, Fin] = [{M}, *, {Fin}], got {tuple(W.shape)}")
+    Fout = int(W.shape[1])
+    f32 = dict(device=x.device, dtype=torch.float32)
+    if residual is not None:
+        _check_dev("residual", residual)
+        residual = residual.contiguous()
+        if residual.numel() != N * M * Fout:
+            raise ValueError(f"residual must be [N, M, Fout] = [{N}, {M}, {Fout}]")
+    xhat = out_xhat if out_xhat is not None else torch.empty((N, M, Fin), **f32)
+    y = out_y if out_y is not None else torch.empty((N, M, Fout), **f32)
+    _check_out("xhat", xhat, (N, M, Fin))
+    _check_out("y", y, (N, M, Fout))
+    if ws is None:
+        ws = torch.empty(fres_workspace_bytes(N, M, Fin, Fout)[0], device=x.device, dtype=torch.uint8)
+    _lib.call("cg_fres_forward_drop", N, M, Fin, Fout, _p(basis), basis.numel(), _p(W), _p(x),
+              float(keep_prob), int(seed) & ((1 << 64) - 1), _p(residual), ACTS[act], _p(xhat), _p(y),
+              _p(ws), ws.numel(), _stream(x))
+    return xhat, y
+
+
+def fres_backward_drop(basis, W, xhat, dy, keep_prob: float, seed: int, y=None, act: str = "none",
+                       need_dz: bool = True, out_dx=None, out_dz=None, out_dW=None, ws=None):
+    """Backward through fres_forward_drop (cg_fres_backward_drop): returns
+    (dx, dW, dz) with dx the gradient of the UNdropped x -- the synthesis stores
+    (acc * mask) / keep_prob, bit for bit ``fres_backward`` then the dropout's
+    backward on dx.  dx is always computed."""
+    _check_keep(keep_prob)
+    for name, t in (("W", W), ("xhat", xhat), ("dy", dy)):
+        _check_dev(name, t)
+    dy, W = dy.contiguous(), W.contiguous()
+    N, M, Fout = (int(s) for s in dy.shape)
+    Fin = int(W.shape[2])
+    f32 = dict(device=dy.device, dtype=torch.float32)
+    if act == "relu":
+        if y is None:
+            raise ValueError("act relu needs the forward's output y")
+        _check_out("y", y, (N, M, Fout))
+    _check_out("xhat", xhat, (N, M, Fin))
+    dx = out_dx if out_dx is not None else torch.empty((N, M, Fin), **f32)
+    _check_out("dx", dx, (N, M, Fin))
+    dz = None
+    if need_dz:
+        dz = out_dz if out_dz is not None else torch.empty((N, M, Fout), **f32)
+        _check_out("dz", dz, (N, M, Fout))
+    dW = out_dW if out_dW is not None else torch.empty((M, Fout, Fin), **f32)
+    _check_out("dW", dW, (M, Fout, Fin))
+    if ws is None:
+        ws = torch.empty(fres_workspace_bytes(N, M, Fin, Fout)[1], device=dy.device, dtype=torch.uint8)
+    _lib.call("cg_fres_backward_drop", N, M, Fin, Fout, _p(basis), basis.numel(), _p(W), _p(xhat),
+              _p(dy), _p(y) if act == "relu" else None, ACTS[act], float(keep_prob),
+              int(seed) & ((1 << 64) - 1), _p(dz), _p(dx), _p(dW), _p(ws), ws.numel(), _stream(dy))
     return dx, dW, dz
 
 

@@ -445,6 +445,36 @@ int cg_fres_backward(int32_t N, int32_t M, int32_t Fin, int32_t Fout, const void
                      float* dW, void* workspace, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * The same block behind a DropoutWrapper (inference_glstm_gconv's conv_init,
+ * lib/gconv_lstm.py:382-389: the filter reads the dropped h_T of the LSTM).
+ * Additive to version 301.
+ *
+ * cg_fres_forward_drop = cg_dropout_forward(x, N*M*Fin, keep_prob, seed) followed
+ * by cg_fres_forward, bit for bit, without the dropped tensor: the analysis
+ * stages element e of x as (x[e] / keep_prob) * floor(keep_prob + u(seed, e)).
+ * xhat is the spectrum of the DROPPED x.
+ *
+ * cg_fres_backward_drop = cg_fres_backward (dx =) followed by
+ * cg_dropout_backward on dx, bit for bit: the synthesis stores
+ * dx[e] = (acc * floor(keep_prob + u(seed, e))) / keep_prob.  dx is required
+ * and there is no dx_accumulate.
+ *
+ * seed: the mask stream of x as a whole tensor; a slice of a larger dropped
+ * tensor passes seed + phi * offset as for cg_dropout_forward.  keep_prob == 1
+ * runs the plain calls.  Workspace: cg_fres_workspace_bytes.  keep_prob outside
+ * (0, 1], a null required pointer (dx included), a short workspace or act RELU
+ * without y return CG_ERR_ARG before any device work.
+ * ------------------------------------------------------------------------- */
+int cg_fres_forward_drop(int32_t N, int32_t M, int32_t Fin, int32_t Fout, const void* basis,
+                         size_t basis_bytes, const float* W, const float* x, float keep_prob,
+                         uint64_t seed, const float* residual, int32_t act, float* xhat, float* y,
+                         void* workspace, size_t ws_bytes, void* stream);
+int cg_fres_backward_drop(int32_t N, int32_t M, int32_t Fin, int32_t Fout, const void* basis,
+                          size_t basis_bytes, const float* W, const float* xhat, const float* dy,
+                          const float* y, int32_t act, float keep_prob, uint64_t seed, float* dz,
+                          float* dx, float* dW, void* workspace, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
  * gconv-LSTM cell pointwise part (lib/gconv_lstm.py:77-221, GConvLSTMCell).
  * The cell's eight cheby_conv calls are two chebyshev5 calls with the four
  * gate weights concatenated: gx = cheb(x; [Wzxt|Wixt|Wfxt|Woxt]) and

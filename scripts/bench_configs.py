@@ -349,6 +349,44 @@ def resgnn_fourier_config(dev, N=100, Fin=10, nfilter=32, nres=4, samples=8):
             "step_transform_TFLOPs_end_to_end": round(step_flop / (s[0] * 1e-3) / 1e12, 1)}
 
 
+def glstm_gconv_config(dev, filter="fourier_conv", T=6, N=50, Fin=2, H=128, C=32, K=2, nres=2,
+                       runs=5):
+    """EG: one GLSTMGconvModel training step at the shape nips2016/gconvTest.py
+    runs (config E's 32 x 32 grid graph, batch 50, filter_num 128,
+    num_hidden_conv 32, kernel_num 2, keep 0.8).  With the Fourier filter the
+    step is timed for seam "fused" and "unfused" (the latter entirely kernels
+    that predate the seam calls) in INTERLEAVED runs: per-run numbers, the
+    medians and the unfused range, which is what "auto" is decided on."""
+    from cnn_graph_amd.glstm_gconv import GLSTMGconvModel
+    _, L = graph_e()
+    M = L.shape[0]
+    seams = ("fused", "unfused") if filter == "fourier_conv" else ("unfused",)
+    models = {s: GLSTMGconvModel(L, N, T, Fin, num_hidden=H, num_hidden_conv=C, K=K, layer_count=1,
+                                 conv_layer_num=nres, keep_prob=0.8, filter=filter, seam=s, device=dev)
+              for s in seams}
+    g = torch.Generator(device=dev)
+    g.manual_seed(6)
+    x = 0.5 * torch.randn((N, M, Fin * T), device=dev, generator=g)
+    labels = torch.randn((N, M, 2), device=dev, generator=g)
+    for m in models.values():  # warm every shape of the timed window
+        for _ in range(3):
+            m.train_step(x, labels)
+    torch.cuda.synchronize()
+    per_run = {s: [] for s in seams}
+    for _ in range(runs):
+        for s in seams:  # interleaved: drift hits both alike
+            per_run[s].append(round(ev_ms(lambda: models[s].train_step(x, labels), 5), 4))
+    out = {"config": "EG", "filter": filter, "M": M, "T": T, "N": N, "Fin": Fin, "H": H, "C": C, "K": K,
+           "conv_layer_num": nres, "keep_prob": 0.8, "runs_ms": per_run,
+           "median_ms": {s: round(float(np.median(v)), 4) for s, v in per_run.items()}}
+    if len(seams) == 2:
+        lo, hi = min(per_run["unfused"]), max(per_run["unfused"])
+        out["unfused_range_ms"] = [lo, hi]
+        out["fused_below_unfused_range"] = bool(out["median_ms"]["fused"] < lo)
+    out["samples_per_s"] = round(N / (min(out["median_ms"].values()) * 1e-3), 1)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("configs", nargs="*", default=["C1", "C2", "D", "E"])
@@ -362,6 +400,8 @@ def main():
                     help="kernel-selection option name=value (cg_set_option), e.g. dw_direct=3")
     ap.add_argument("--copy-x", action="store_true",
                     help="planes layout: keep x in its own buffer (the forward copies it into plane 0)")
+    ap.add_argument("--filter", default="fourier_conv", choices=["fourier_conv", "cheby_conv"],
+                    help="EG: the filter of the cells and the head")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline legs")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     args = ap.parse_args()
@@ -413,6 +453,8 @@ def main():
             out = lstm_config(dev, hconv="fused")
         elif name == "RF":
             out = resgnn_fourier_config(dev)
+        elif name == "EG":
+            out = glstm_gconv_config(dev, filter=args.filter)
         elif name == "R":
             out = resgnn_config(dev)
             cpu = lambda: bench.cpu_baseline_resgnn(graph_e()[1], 2, 100, 2, 32, 20, 4,  # noqa: E731
