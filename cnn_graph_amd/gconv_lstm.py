@@ -20,8 +20,12 @@ Reference behaviour kept:
     go through ``tf.nn.dropout`` on a HIP kernel (``ops.dropout``); every
     wrapper draws its own mask stream (a distinct seed per wrapper unless one
     is given), as each TF DropoutWrapper owns an independent random op.
+  * ``LSTMStackTrainer``: glstm_layer's cells and wrappers with their parameters
+    carved from ``trainer.FlatTrainer``'s flat buffers, and ``lstm_to_hT``, the
+    walk to the last step's output -- shared by ``GLSTMModel`` and
+    ``glstm_gconv.GLSTMGconvModel``.
   * ``GLSTMModel``: ``inference_glstm`` (:271-281) -- glstm_layer, the last
-    step's output, ``fc_layer`` (:629-636) -- with the MSE loss and the
+    step's output, ``fc_layer`` (:629-636) -- with FlatTrainer's MSE loss and
     optimizer step (lib/graph_model.py:246-310; sgd / rmsprop of
     lib/gconvRNN.py:381-389), data parallel with ONE all-reduce of a flat
     gradient bucket per step (config E: batch 512 over 4 GPUs).
@@ -72,7 +76,6 @@ the bias gradient are per layer:
 from __future__ import annotations
 
 import collections
-import ctypes
 import itertools
 import math
 
@@ -82,6 +85,7 @@ from . import _lib
 from . import ops
 from .graph_conv import truncated_normal_
 from .plan import plan_for
+from .trainer import FlatTrainer
 
 # distinct default mask streams per DropoutWrapper (TF: one random op each)
 _DROPOUT_ORDINAL = itertools.count(1)
@@ -738,7 +742,95 @@ def dropout_seed(seed: int, rank: int, layer: int) -> int:
     return z ^ (z >> 31)
 
 
-class GLSTMModel:
+def lstm_to_hT(cells, wrapped, xs, dropout: bool):
+    """static_rnn(wrapped, xs) then outputs[-1], with the last layer's sequence
+    read at its last step only.  Returns (h_T, mask): that layer runs unwrapped,
+    and its h_T (a separate output: the backward gets no zero [T, N, M, H]
+    gradient) is still to go through ``mask`` = (keep_prob, seed, offset), the
+    last-step slice of the layer's mask stream (element offset (T-1) N M H) --
+    the values and gradients of the whole-sequence form, 1/T of its dropout
+    traffic.  The caller applies it (``ops.dropout``) or folds it into what
+    reads h_T.  ``dropout=False`` runs every layer unwrapped; mask is None then,
+    and when the layers have no wrapper."""
+    last = len(cells) - 1
+    for li in range(last):
+        xs, _ = layer(wrapped[li] if dropout else cells[li], xs, final_c=False)
+    _, st = layer(cells[last], xs, final_c=False)
+    w = wrapped[last]
+    if dropout and isinstance(w, DropoutWrapper):
+        return st.h, (w.output_keep_prob, w.next_seed(), (xs.shape[0] - 1) * st.h.numel())
+    return st.h, None
+
+
+class LSTMStackTrainer(FlatTrainer):
+    """The part ``GLSTMModel`` and ``GLSTMGconvModel`` share: ``glstm_layer``
+    (lib/gconv_lstm.py:609-627) -- layer_count GConvLSTMCells, each in a
+    DropoutWrapper(keep_prob) -- with every cell's Wx, Wh, b carved from the flat
+    buffers first, as autograd-owned Parameters whose ``.grad`` is the bucket
+    view.  ``tail_numel`` parameters follow, for the subclass to carve (drawing
+    from ``self._gen``, after the cells' own initial draws)."""
+
+    def __init__(self, L, N, T, feat_in, num_hidden, K, layer_count, out_features, keep_prob, filter,
+                 tail_numel, optimizer, learning_rate, decay_rate, decay_steps, lmax, gates, device,
+                 seed, comm):
+        if filter not in ("cheby_conv", "fourier_conv"):
+            raise ValueError("filter must be 'cheby_conv' or 'fourier_conv'")
+        self.filter = filter
+        self.N, self.T, self.F, self.H, self.K = int(N), int(T), int(feat_in), int(num_hidden), int(K)
+        self.Fout = int(out_features)
+        device = torch.device(device if device is not None else "cuda")
+        self._gen = gen = torch.Generator(device=device)
+        gen.manual_seed(seed)
+        cells = [GConvLSTMCell(self.H, laplacian=L, lmax=lmax, K=self.K,
+                               feat_in=self.F if li == 0 else self.H, gates=gates, device=device,
+                               generator=gen, filter_type=filter) for li in range(int(layer_count))]
+        self.M = cells[0]._nNode
+        super().__init__(sum(p.numel() for c in cells for p in c.parameters()) + tail_numel,
+                         (self.N, self.M, self.Fout), optimizer, learning_rate, decay_rate, decay_steps,
+                         device, comm)
+        fourier = filter == "fourier_conv"
+        self.plan = None if fourier else cells[0].plan
+        self.U = cells[0].U if fourier else None
+        for li, c in enumerate(cells):
+            for n in ("Wx", "Wh", "b"):
+                t = getattr(c, n).detach()
+                name = f"gconv_lstm_layer/rnn/multi_rnn_cell/cell_{li}/{n}"
+                setattr(c, n, self.carve(t.shape, name, init=t)[0])
+        self.cells = cells
+        # each wrapper's mask stream from (model seed, rank, layer): training is
+        # reproducible from the seed, and the ranks draw independent masks for
+        # their shards (TF: one random op per wrapper per replica)
+        rank = int(getattr(comm, "rank", 0)) if comm is not None else 0
+        self.wrapped = [DropoutWrapper(c, keep_prob, seed=dropout_seed(seed, rank, li))
+                        if keep_prob < 1.0 else c for li, c in enumerate(cells)]
+
+    def _steps(self, x):
+        if x.dim() == 3:  # [N, M, F*T] as the reference feeds it
+            return unstack_time(x, self.T)
+        return x.contiguous()
+
+    def predict(self, data, labels=None, reference_dropout: bool = False):
+        """GraphModel.predict (lib/graph_model.py:64-94; evaluate.predict has the
+        padding and the ``loss * batch_size / size`` quirk, padded rows
+        included): data [size, M, F*T] -> predictions [size, M, out_features],
+        with labels also the loss.  Parameters, optimizer slots, the loss
+        average and the step count are untouched.
+
+        Dropout at evaluation: the reference's DropoutWrapper(0.8) inside
+        glstm_layer (lib/gconv_lstm.py:616, :623) is a constant of the graph, so
+        the reference ALSO drops when it evaluates.  The default here is no
+        dropout (deterministic predictions); ``reference_dropout=True`` applies
+        the wrappers' masks as a training forward does (and advances their
+        mask streams)."""
+        return super().predict(data, labels, dropout=reference_dropout)
+
+    def evaluate(self, data, labels, reference_dropout: bool = False):
+        """GraphModel.evaluate (lib/graph_model.py:96-122):
+        (string, mse, 0, loss, predictions)."""
+        return super().evaluate(data, labels, dropout=reference_dropout)
+
+
+class GLSTMModel(LSTMStackTrainer):
     """``GconvModel.inference_glstm`` (lib/gconv_lstm.py:271-281) trained as
     ``GraphModel`` trains it (lib/graph_model.py:246-310):
 
@@ -748,10 +840,9 @@ class GLSTMModel:
       fc_layer       out = cheby_conv(outputs[-1]; W_fc [K*H, Fout]) (:629-636); with
                      filter="fourier_conv" the cells and the fc layer use the
                      Fourier filter (Wx [M, 4H, Fin], Wh [M, 4H, H], W_fc [M, Fout, H])
-      loss           mean((labels - out)^2) + its moving average    cg_mse_loss_ema
-      exchange       ONE all-reduce(sum) of the flat gradient bucket (N > 1)
-      update         ONE optimizer launch over the flat parameter buffer,
-                     grad_scale = 1/world: Adam (graph_model.py:293, staircase
+      loss / exchange / update   FlatTrainer's: cg_mse_loss_ema, ONE all-reduce(sum)
+                     of the flat gradient bucket (world > 1), ONE optimizer launch
+                     with grad_scale = 1/world: Adam (graph_model.py:293, staircase
                      exponential decay) or gconvRNN's sgd / rmsprop
                      (lib/gconvRNN.py:381-389)
 
@@ -759,212 +850,42 @@ class GLSTMModel:
     W_fc) is a view into one flat fp32 buffer and its ``.grad`` a view into one
     flat gradient bucket that autograd accumulates into in place -- at config E
     (Fin 2, H 32, K 3, one layer) 13 376 floats = 53.5 KB -- so the data-parallel
-    exchange of a step is one collective and the update one launch.
-    ``comm`` is any object with ``allreduce_sum_(tensor, stream)`` and ``world``
-    (``dist.RcclComm`` on RCCL, ``dist.TorchComm`` on a process group)."""
-
-    OPTIMIZERS = ("adam", "sgd", "rmsprop")
+    exchange of a step is one collective and the update one launch."""
 
     def __init__(self, L, N: int, T: int, feat_in: int, num_hidden: int = 32, K: int = 3,
                  layer_count: int = 1, out_features: int = 2, keep_prob: float = 0.8,
                  optimizer: str = "adam", learning_rate: float = 1e-3, decay_rate: float = 0.95,
                  decay_steps: int | None = None, lmax: float = 2, gates: str = "reference",
                  device=None, seed: int = 2017, comm=None, filter: str = "cheby_conv"):
-        if optimizer not in self.OPTIMIZERS:
-            raise ValueError(f"optimizer must be one of {self.OPTIMIZERS}")
-        if filter not in ("cheby_conv", "fourier_conv"):
-            raise ValueError("filter must be 'cheby_conv' or 'fourier_conv'")
-        self.filter = filter
-        self.device = torch.device(device if device is not None else "cuda")
-        self.N, self.T, self.F, self.H, self.K = int(N), int(T), int(feat_in), int(num_hidden), int(K)
-        self.Fout = int(out_features)
-        self.optimizer, self.lr = optimizer, learning_rate
-        self.decay_rate, self.decay_steps = decay_rate, decay_steps
-        self.comm = comm
-        gen = torch.Generator(device=self.device)
-        gen.manual_seed(seed)
-        cells = []
-        for li in range(int(layer_count)):
-            fin = self.F if li == 0 else self.H
-            cells.append(GConvLSTMCell(self.H, laplacian=L, lmax=lmax, K=self.K, feat_in=fin,
-                                       gates=gates, device=self.device, generator=gen,
-                                       filter_type=filter))
-        fourier = filter == "fourier_conv"
-        self.plan = None if fourier else cells[0].plan
-        self.U = cells[0].U if fourier else None
-        self.M = cells[0]._nNode
-        H, K = self.H, self.K
         # fc_layer (lib/gconv_lstm.py:629-636) uses the same filter by name
-        fc_shape = (self.M, self.Fout, H) if fourier else (K * H, self.Fout)
-        sizes = [c.Wx.numel() + c.Wh.numel() + c.b.numel() for c in cells] + [math.prod(fc_shape)]
-        f32 = dict(device=self.device, dtype=torch.float32)
-        total = sum(sizes)
-        self.flat = torch.empty(total, **f32)
-        self.grad = torch.zeros(total, **f32)
-        self.names, self.params = [], []
-        off = 0
+        H, Fout = int(num_hidden), int(out_features)
+        fc_shape = (int(L.shape[0]), Fout, H) if filter == "fourier_conv" else (int(K) * H, Fout)
+        super().__init__(L, N, T, feat_in, num_hidden, K, layer_count, out_features, keep_prob, filter,
+                         math.prod(fc_shape), optimizer, learning_rate, decay_rate, decay_steps, lmax,
+                         gates, device, seed, comm)
+        w0 = truncated_normal_(torch.empty(fc_shape, device=self.device, dtype=torch.float32), 0.1,
+                               self._gen)
+        self.W_fc = self.carve(fc_shape, "conv_init/weights", init=w0)[0]
+        self._carved()
 
-        def bind(t_init, name):
-            nonlocal off
-            n = t_init.numel()
-            view = self.flat[off:off + n].view_as(t_init)
-            view.copy_(t_init)
-            p = torch.nn.Parameter(view)   # aliases the flat buffer
-            p.grad = self.grad[off:off + n].view_as(t_init)
-            off += n
-            self.names.append(name)
-            self.params.append(p)
-            return p
-
-        scope = "gconv_lstm_layer/rnn/multi_rnn_cell/cell_{}/"
-        for li, c in enumerate(cells):
-            with torch.no_grad():
-                c.Wx = bind(c.Wx.detach(), scope.format(li) + "Wx")
-                c.Wh = bind(c.Wh.detach(), scope.format(li) + "Wh")
-                c.b = bind(c.b.detach(), scope.format(li) + "b")
-        with torch.no_grad():
-            w0 = truncated_normal_(torch.empty(fc_shape, **f32), 0.1, gen)
-            self.W_fc = bind(w0, "conv_init/weights")
-        assert off == total
-        self.cells = cells
-        # each wrapper's mask stream from (model seed, rank, layer): training is
-        # reproducible from the seed, and the ranks draw independent masks for
-        # their shards (TF: one random op per wrapper per replica)
-        rank = int(getattr(comm, "rank", 0)) if comm is not None else 0
-        self.wrapped = [DropoutWrapper(c, keep_prob, seed=dropout_seed(seed, rank, li))
-                        if keep_prob < 1.0 else c for li, c in enumerate(cells)]
-        # optimizer slots (TF 1.x: Adam m, v zeros; RMSProp ms ONES, mom zeros)
-        self.s1 = (torch.ones if optimizer == "rmsprop" else torch.zeros)(total, **f32)
-        self.s2 = torch.zeros(total, **f32)
-        self.loss = torch.empty((1,), **f32)
-        self.ema = torch.zeros((3,), **f32)  # ExponentialMovingAverage(0.9) of the loss
-        self.dout = torch.empty((self.N, self.M, self.Fout), **f32)
-        nb = ctypes.c_size_t()
-        _lib.call("cg_mse_loss_workspace_bytes", self.N * self.M * self.Fout, ctypes.byref(nb))
-        self.mws = torch.empty(max(nb.value, 1), device=self.device, dtype=torch.uint8)
-        self.mws_n = nb.value
-        self.step_count = 0
-
-    @property
-    def world(self):
-        return self.comm.world if self.comm is not None else 1
-
-    @property
-    def loss_average(self):
-        return self.ema[1:2]
-
-    def parameters(self):
-        return dict(zip(self.names, self.params))
-
-    def gradients(self):
-        return dict(zip(self.names, (p.grad for p in self.params)))
-
-    def learning_rate(self, step):
-        """tf.train.exponential_decay(lr, global_step, decay_steps, decay_rate, staircase=True)."""
-        if self.decay_rate == 1 or not self.decay_steps:
-            return self.lr
-        return self.lr * self.decay_rate ** math.floor(step / self.decay_steps)
-
-    def _steps(self, x):
-        if x.dim() == 3:  # [N, M, F*T] as the reference feeds it
-            return unstack_time(x, self.T)
-        return x.contiguous()
-
-    def forward(self, x):
-        """inference_glstm: the fc layer's output [N, M, out_features].
-
-        static_rnn(self.wrapped, ...) then outputs[-1], with the last layer's
-        sequence read at its last step only: that layer runs unwrapped, its
-        h_T (a separate output: the backward gets no zero [T, N, M, H]
-        gradient) goes through the dropout as the last-step slice of the
-        layer's mask (same seed, element offset (T-1)*N*M*H) -- the values
-        and gradients of the whole-sequence form, 1/T of its dropout traffic."""
-        xs = self._steps(x)
-        last = len(self.wrapped) - 1
-        for li, cell in enumerate(self.wrapped):
-            if li < last:
-                xs, _ = layer(cell, xs, final_c=False)
-                continue
-            drop = isinstance(cell, DropoutWrapper)
-            _, st = layer(cell.cell if drop else cell, xs, final_c=False)
-            h = st.h
-            if drop:
-                h = ops.dropout(h, cell.output_keep_prob, cell.next_seed(),
-                                offset=(xs.shape[0] - 1) * h.numel())
+    def forward(self, x, dropout: bool = True):
+        """inference_glstm: the fc layer's output [N, M, out_features] (lstm_to_hT,
+        the last-step mask through ops.dropout, fc_layer).  ``dropout=False``
+        runs every layer unwrapped."""
+        h, mask = lstm_to_hT(self.cells, self.wrapped, self._steps(x), dropout)
+        if mask is not None:
+            keep, seed, off = mask
+            h = ops.dropout(h, keep, seed, offset=off)
         if self.filter == "fourier_conv":
             return ops.fourier_conv(h, self.W_fc, self.U)
         return ops.cheb_conv(h, self.W_fc, self.plan, self.K)
 
     def train_step(self, x, labels, stream=None):
         """One optimizer step; returns the device loss [1] (this rank's batch)."""
-        s = stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream
+        s = self._stream(stream)
         self.grad.zero_()
         out = self.forward(x)
-        labels = labels.contiguous()
-        if labels.numel() != out.numel():
-            raise ValueError("labels must match the logits' shape")
-        _lib.call("cg_mse_loss_ema", out.data_ptr(), labels.data_ptr(), out.numel(),
-                  self.loss.data_ptr(), self.dout.data_ptr(), self.ema.data_ptr(),
-                  ctypes.c_float(0.9), self.mws.data_ptr(), self.mws_n, s)
+        self._loss(out, labels, s)
         out.backward(self.dout)
-        _exchange_and_update(self, s)
+        self._exchange_and_update(s)
         return self.loss
-
-    def predict(self, data, labels=None, reference_dropout: bool = False):
-        """GraphModel.predict (lib/graph_model.py:64-94; evaluate.predict has the
-        padding and the ``loss * batch_size / size`` quirk): data [size, M, F*T]
-        -> predictions [size, M, out_features], with labels also the loss.
-
-        Dropout at evaluation: the reference's DropoutWrapper(0.8) inside
-        glstm_layer is a constant of the graph, so the reference ALSO drops
-        when it evaluates.  Here the default is no dropout (deterministic
-        predictions); ``reference_dropout=True`` applies the wrappers' masks as
-        a training forward does (and advances their mask streams)."""
-        from . import evaluate as _ev
-
-        def fwd(batch):
-            wrapped = self.wrapped
-            if not reference_dropout:
-                self.wrapped = self.cells
-            try:
-                return self.forward(batch)
-            finally:
-                self.wrapped = wrapped
-
-        return _ev.predict(fwd, self.N, self.device, data, labels)
-
-    def evaluate(self, data, labels, reference_dropout: bool = False):
-        """GraphModel.evaluate (lib/graph_model.py:96-122):
-        (string, mse, 0, loss, predictions)."""
-        from . import evaluate as _ev
-        return _ev.evaluate(lambda d, l: self.predict(d, l, reference_dropout), data, labels)
-
-
-def _exchange_and_update(m, s):
-    """The tail of a flat-bucket training step (GLSTMModel, GLSTMGconvModel):
-    every .grad still inside the bucket, ONE all-reduce when world > 1, ONE
-    optimizer launch with grad_scale = 1/world."""
-    for p in m.params:  # autograd accumulated into the flat bucket in place
-        if p.grad is None or p.grad.data_ptr() < m.grad.data_ptr() or \
-                p.grad.data_ptr() >= m.grad.data_ptr() + 4 * m.grad.numel():
-            raise RuntimeError("a parameter's .grad left the flat gradient bucket")
-    world = 1
-    if m.comm is not None and m.comm.world > 1:
-        m.comm.allreduce_sum_(m.grad, s)
-        world = m.comm.world
-    m.step_count += 1
-    lr = m.learning_rate(m.step_count - 1)
-    n = m.flat.numel()
-    if m.optimizer == "adam":
-        _lib.call("cg_adam_update", m.flat.data_ptr(), m.grad.data_ptr(), m.s1.data_ptr(),
-                  m.s2.data_ptr(), n, ctypes.c_float(lr), ctypes.c_float(0.9),
-                  ctypes.c_float(0.999), ctypes.c_float(1e-8), m.step_count,
-                  ctypes.c_float(1.0 / world), s)
-    elif m.optimizer == "sgd":
-        _lib.call("cg_sgd_update", m.flat.data_ptr(), m.grad.data_ptr(), n,
-                  ctypes.c_float(lr), ctypes.c_float(1.0 / world), s)
-    else:
-        _lib.call("cg_rmsprop_update", m.flat.data_ptr(), m.grad.data_ptr(),
-                  m.s1.data_ptr(), m.s2.data_ptr(), n, ctypes.c_float(lr),
-                  ctypes.c_float(0.9), ctypes.c_float(0.0), ctypes.c_float(1e-10),
-                  ctypes.c_float(1.0 / world), s)

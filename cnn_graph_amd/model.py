@@ -20,9 +20,11 @@
   exchange     one all-reduce of the flat gradient buffer (RcclComm, N > 1)
   update       ONE cg_adam_update over the flat parameter buffer (grad / world)
 
-Every weight is a view into one flat fp32 buffer (and so is every gradient),
-so the optimizer and the data-parallel exchange are one launch each.  No
-PyTorch compute op runs in the step: torch only owns the buffers.
+Loss, exchange, update, the flat buffers and predict / evaluate are
+``trainer.FlatTrainer``'s, shared with the gconv-LSTM models: every weight is a
+view into one flat fp32 buffer (and so is every gradient), so the optimizer and
+the data-parallel exchange are one launch each.  No PyTorch compute op runs in
+the step: torch only owns the buffers.
 Weights: ``truncated_normal(0, 0.1)`` per ``tf.get_variable('weights')``
 (lib/graph_model.py:326-333) in the reference's scope order.
 
@@ -51,91 +53,106 @@ from . import filter as _filter
 from . import ops
 from .graph_conv import truncated_normal_
 from .plan import plan_for
+from .trainer import FlatTrainer
+
+
+def _chain(scope, Fin, F, R, Fout_last):
+    """(name, Fin, Fout, act) of a residual network's filters in the reference's call order."""
+    layers = [(f"{scope}conv_init/weights", Fin, F, "relu")]
+    for i in range(R):
+        layers.append((f"{scope}residual_layer_{i}/sublayer0/weights", F, F, "relu"))
+        layers.append((f"{scope}residual_layer_{i}/sublayer1/weights", F, F, "relu"))
+    layers.append((f"{scope}convN/weights", F, Fout_last, "none"))
+    return layers
 
 
 class _ResNet:
     """One ``residual_network`` (lib/graph_conv.py:305-330): conv_init, R
-    residual layers of two filters each, convN.  Its weights and gradients are
-    views into the owner's flat buffers starting at ``off``.
+    residual layers of two filters each, convN, on the Chebyshev filter.  Its
+    weights and gradients are the next views the owner's ``carve`` hands out,
+    drawn ``truncated_normal(0, 0.1)`` from ``gen`` in creation order.
+
+    What a net reads from its ``owner`` (a FlatTrainer), and nothing else: the
+    batch and graph sizes ``N`` and ``M``, ``device``, the Chebyshev ``plan`` (the
+    prepared basis ``gft`` for the Fourier net), the flat buffers through
+    ``carve``, and the workspace ``ws`` / ``ws_n`` at call time.
 
     ``input_grad``: the input is an activation, not data (the network sits
     behind an LSTM, lib/gconv_lstm.py:382-389): conv_init's backward also
     computes dx into ``dx_in`` [N, M, Fin].  ``names`` replaces the variable
     names (same order)."""
 
-    def __init__(self, owner, scope: str, Fin: int, off: int, gen, input_grad: bool = False,
-                 names=None):
+    def __init__(self, owner, scope: str, Fin: int, nfilter: int, K: int, R: int, Fout_last: int, gen,
+                 input_grad: bool = False, names=None):
         self.o = owner
-        N, M, K, F = owner.N, owner.M, owner.K, owner.nfilter
-        # (scope, Fin, Fout, act) in the reference's call order
-        layers = [(f"{scope}conv_init/weights", Fin, F, "relu")]
-        for i in range(owner.R):
-            layers.append((f"{scope}residual_layer_{i}/sublayer0/weights", F, F, "relu"))
-            layers.append((f"{scope}residual_layer_{i}/sublayer1/weights", F, F, "relu"))
-        layers.append((f"{scope}convN/weights", F, owner.Fout_last, "none"))
-        self.layers = layers
-        self.Fin = Fin
-        f32 = dict(device=owner.device, dtype=torch.float32)
+        N, M = owner.N, owner.M
+        self.Fin, self.K, self.R = Fin, K, R
+        self.layers = layers = _chain(scope, Fin, nfilter, R, Fout_last)
+        self.names = list(names) if names is not None else [name for name, *_ in layers]
+        if len(self.names) != len(layers):
+            raise ValueError(f"{len(layers)} filters, {len(self.names)} names")
         self.W, self.dW = [], []
-        for _, fi, fo, _ in layers:
-            sz = fi * K * fo
-            w = owner.flat[off:off + sz].view(fi * K, fo)
+        for name, (_, fi, fo, _) in zip(self.names, layers):
+            w, dw = owner.carve(self._wshape(fi, fo, K, M), name)
             truncated_normal_(w, 0.1, gen)
             self.W.append(w)
-            self.dW.append(owner.grad[off:off + sz].view(fi * K, fo))
-            off += sz
-        self.end = off
-        self._finish(names, input_grad, f32)
-        # activations / bases saved by the forward, gradient work buffers; the
-        # basis layout per filter: planes where it applies, else rows
-        self.layout = ["planes" if owner.plan.basis_elems(N, fi, K, fo, "planes") else "rows"
-                       for _, fi, fo, _ in layers]
-        self.basis = [torch.empty((K, N * M, fi) if lay == "planes" else (N * M, fi * K), **f32)
-                      for (_, fi, _, _), lay in zip(layers, self.layout)]
-        self.out = [torch.empty((N, M, fo), **f32) for _, _, fo, _ in layers]
-        self.g = [torch.empty((N, M, F), **f32) for _ in range(3)]
-
-    def _finish(self, names, input_grad, f32):
-        self.names = list(names) if names is not None else [name for name, *_ in self.layers]
-        if len(self.names) != len(self.layers):
-            raise ValueError(f"{len(self.layers)} filters, {len(self.names)} names")
+            self.dW.append(dw)
+        f32 = dict(device=owner.device, dtype=torch.float32)
         self.input_grad = bool(input_grad)
-        self.dx_in = torch.empty((self.o.N, self.o.M, self.Fin), **f32) if input_grad else None
+        self.dx_in = torch.empty((N, M, Fin), **f32) if input_grad else None
+        # activations saved by the forward, gradient work buffers
+        self.out = [torch.empty((N, M, fo), **f32) for _, _, fo, _ in layers]
+        self.g = [torch.empty((N, M, nfilter), **f32) for _ in range(3)]
+        self._setup(f32)
 
     @staticmethod
-    def sizes(Fin, F, K, R, Fout_last):
-        return [Fin * K * F] + [F * K * F] * (2 * R) + [F * K * Fout_last]
+    def _wshape(fi, fo, K, M):
+        return (fi * K, fo)
+
+    @classmethod
+    def sizes(cls, Fin, F, K, M, R, Fout_last):
+        """Parameter counts of the filters, in creation order."""
+        return [math.prod(cls._wshape(fi, fo, K, M)) for _, fi, fo, _ in _chain("", Fin, F, R, Fout_last)]
+
+    def _setup(self, f32):
+        """The filter's saved tensors and C entry points: the Chebyshev bases, in
+        the planes layout where it applies, else rows."""
+        o, N, M, K = self.o, self.o.N, self.o.M, self.K
+        self.layout = ["planes" if o.plan.basis_elems(N, fi, K, fo, "planes") else "rows"
+                       for _, fi, fo, _ in self.layers]
+        self.basis = [torch.empty((K, N * M, fi) if lay == "planes" else (N * M, fi * K), **f32)
+                      for (_, fi, _, _), lay in zip(self.layers, self.layout)]
+        h = _lib.lib()
+        self._fwd, self._bwd = h.cg_cheb_forward_layout, h.cg_cheb_backward_layout
 
     def ws_bytes(self):
         o = self.o
-        fb = max(o.plan.workspace_bytes(o.N, fi, o.K, fo)[0] for _, fi, fo, _ in self.layers)
-        bb = max(o.plan.workspace_bytes(o.N, fi, o.K, fo)[1] for _, fi, fo, _ in self.layers)
-        return max(fb, bb)
+        return max(max(o.plan.workspace_bytes(o.N, fi, self.K, fo)) for _, fi, fo, _ in self.layers)
 
     def _f(self, li, x, res, s):
         o = self.o
         _, fi, fo, act = self.layers[li]
-        st = o._fwd(o.plan.handle, o.N, fi, o.K, fo, x.data_ptr(), self.W[li].data_ptr(),
-                    res.data_ptr() if res is not None else None, ops.ACTS[act],
-                    _lib.BASIS_LAYOUTS[self.layout[li]], self.basis[li].data_ptr(),
-                    self.out[li].data_ptr(), o.ws.data_ptr(), o.ws_n, s)
+        st = self._fwd(o.plan.handle, o.N, fi, self.K, fo, x.data_ptr(), self.W[li].data_ptr(),
+                       res.data_ptr() if res is not None else None, ops.ACTS[act],
+                       _lib.BASIS_LAYOUTS[self.layout[li]], self.basis[li].data_ptr(),
+                       self.out[li].data_ptr(), o.ws.data_ptr(), o.ws_n, s)
         _lib.check("cg_cheb_forward_layout", st)
         return self.out[li]
 
     def _b(self, li, dy, dz, dx, dx_acc, s):
         o = self.o
         _, fi, fo, act = self.layers[li]
-        st = o._bwd(o.plan.handle, o.N, fi, o.K, fo, dy.data_ptr(), self.out[li].data_ptr(),
-                    ops.ACTS[act], _lib.BASIS_LAYOUTS[self.layout[li]], self.basis[li].data_ptr(),
-                    self.W[li].data_ptr(), dx.data_ptr() if dx is not None else None, int(dx_acc),
-                    self.dW[li].data_ptr(), dz.data_ptr() if dz is not None else None,
-                    o.ws.data_ptr(), o.ws_n, s)
+        st = self._bwd(o.plan.handle, o.N, fi, self.K, fo, dy.data_ptr(), self.out[li].data_ptr(),
+                       ops.ACTS[act], _lib.BASIS_LAYOUTS[self.layout[li]], self.basis[li].data_ptr(),
+                       self.W[li].data_ptr(), dx.data_ptr() if dx is not None else None, int(dx_acc),
+                       self.dW[li].data_ptr(), dz.data_ptr() if dz is not None else None,
+                       o.ws.data_ptr(), o.ws_n, s)
         _lib.check("cg_cheb_backward_layout", st)
 
     def forward(self, x, s):
         h = self._f(0, x, None, s)
         li = 1
-        for _ in range(self.o.R):
+        for _ in range(self.R):
             t = self._f(li, h, None, s)
             h = self._f(li + 1, t, h, s)
             li += 2
@@ -150,7 +167,7 @@ class _ResNet:
         self._b(last, dout, None, dh, False, s)            # convN: dh = dL/dh
         cur = 0  # bufs[cur] is dh
         li = last - 2
-        for _ in range(self.o.R):
+        for _ in range(self.R):
             dz1 = bufs[(cur + 1) % 3]
             dt = bufs[(cur + 2) % 3]
             self._b(li + 1, dh, dz1, dt, False, s)         # sublayer1: dz1 = dh*[h'>0] (= d residual)
@@ -164,7 +181,8 @@ class _ResNet:
 class _FourierResNet(_ResNet):
     """The same network with the Fourier filter: _ResNet's forward / backward
     schedule over cg_fres_forward / cg_fres_backward.  Weights [M, Fout, Fin]
-    (lib/graph_conv.py:105); the forward saves each filter's spectrum xhat.
+    (lib/graph_conv.py:105); the forward saves each filter's spectrum xhat; ``K``
+    is ignored.
 
     ``drop`` = (keep_prob, seed) or None: conv_init reads its input through a
     dropout mask folded into the transforms (cg_fres_forward_drop /
@@ -172,35 +190,15 @@ class _FourierResNet(_ResNet):
 
     drop = None
 
-    def __init__(self, owner, scope: str, Fin: int, off: int, gen, input_grad: bool = False,
-                 names=None):
-        self.o = owner
-        N, M, F = owner.N, owner.M, owner.nfilter
-        layers = [(f"{scope}conv_init/weights", Fin, F, "relu")]
-        for i in range(owner.R):
-            layers.append((f"{scope}residual_layer_{i}/sublayer0/weights", F, F, "relu"))
-            layers.append((f"{scope}residual_layer_{i}/sublayer1/weights", F, F, "relu"))
-        layers.append((f"{scope}convN/weights", F, owner.Fout_last, "none"))
-        self.layers = layers
-        self.Fin = Fin
-        f32 = dict(device=owner.device, dtype=torch.float32)
-        self.W, self.dW = [], []
-        for _, fi, fo, _ in layers:
-            sz = M * fo * fi
-            w = owner.flat[off:off + sz].view(M, fo, fi)
-            truncated_normal_(w, 0.1, gen)
-            self.W.append(w)
-            self.dW.append(owner.grad[off:off + sz].view(M, fo, fi))
-            off += sz
-        self.end = off
-        self._finish(names, input_grad, f32)
-        self.xhat = [torch.empty((N, M, fi), **f32) for _, fi, _, _ in layers]
-        self.out = [torch.empty((N, M, fo), **f32) for _, _, fo, _ in layers]
-        self.g = [torch.empty((N, M, F), **f32) for _ in range(3)]
-
     @staticmethod
-    def sizes(Fin, F, M, R, Fout_last):
-        return [M * F * Fin] + [M * F * F] * (2 * R) + [M * Fout_last * F]
+    def _wshape(fi, fo, K, M):
+        return (M, fo, fi)
+
+    def _setup(self, f32):
+        self.xhat = [torch.empty((self.o.N, self.o.M, fi), **f32) for _, fi, _, _ in self.layers]
+        h = _lib.lib()
+        self._fwd, self._bwd = h.cg_fres_forward, h.cg_fres_backward
+        self._fwd_drop, self._bwd_drop = h.cg_fres_forward_drop, h.cg_fres_backward_drop
 
     def ws_bytes(self):
         o = self.o
@@ -211,15 +209,15 @@ class _FourierResNet(_ResNet):
         _, fi, fo, act = self.layers[li]
         if li == 0 and self.drop is not None:
             keep, seed = self.drop
-            st = _lib.lib().cg_fres_forward_drop(
+            st = self._fwd_drop(
                 o.N, o.M, fi, fo, o.gft.data_ptr(), o.gft.numel(), self.W[li].data_ptr(), x.data_ptr(),
                 ctypes.c_float(keep), seed, None, ops.ACTS[act], self.xhat[li].data_ptr(),
                 self.out[li].data_ptr(), o.ws.data_ptr(), o.ws_n, s)
             _lib.check("cg_fres_forward_drop", st)
             return self.out[li]
-        st = o._fwd(o.N, o.M, fi, fo, o.gft.data_ptr(), o.gft.numel(), self.W[li].data_ptr(),
-                    x.data_ptr(), res.data_ptr() if res is not None else None, ops.ACTS[act],
-                    self.xhat[li].data_ptr(), self.out[li].data_ptr(), o.ws.data_ptr(), o.ws_n, s)
+        st = self._fwd(o.N, o.M, fi, fo, o.gft.data_ptr(), o.gft.numel(), self.W[li].data_ptr(),
+                       x.data_ptr(), res.data_ptr() if res is not None else None, ops.ACTS[act],
+                       self.xhat[li].data_ptr(), self.out[li].data_ptr(), o.ws.data_ptr(), o.ws_n, s)
         _lib.check("cg_fres_forward", st)
         return self.out[li]
 
@@ -228,7 +226,7 @@ class _FourierResNet(_ResNet):
         _, fi, fo, act = self.layers[li]
         if li == 0 and self.drop is not None:
             keep, seed = self.drop
-            st = _lib.lib().cg_fres_backward_drop(
+            st = self._bwd_drop(
                 o.N, o.M, fi, fo, o.gft.data_ptr(), o.gft.numel(), self.W[li].data_ptr(),
                 self.xhat[li].data_ptr(), dy.data_ptr(), self.out[li].data_ptr(), ops.ACTS[act],
                 ctypes.c_float(keep), seed, dz.data_ptr() if dz is not None else None,
@@ -236,33 +234,32 @@ class _FourierResNet(_ResNet):
                 o.ws_n, s)
             _lib.check("cg_fres_backward_drop", st)
             return
-        st = o._bwd(o.N, o.M, fi, fo, o.gft.data_ptr(), o.gft.numel(), self.W[li].data_ptr(),
-                    self.xhat[li].data_ptr(), dy.data_ptr(), self.out[li].data_ptr(), ops.ACTS[act],
-                    dz.data_ptr() if dz is not None else None,
-                    dx.data_ptr() if dx is not None else None, int(dx_acc),
-                    self.dW[li].data_ptr(), o.ws.data_ptr(), o.ws_n, s)
+        st = self._bwd(o.N, o.M, fi, fo, o.gft.data_ptr(), o.gft.numel(), self.W[li].data_ptr(),
+                       self.xhat[li].data_ptr(), dy.data_ptr(), self.out[li].data_ptr(), ops.ACTS[act],
+                       dz.data_ptr() if dz is not None else None,
+                       dx.data_ptr() if dx is not None else None, int(dx_acc),
+                       self.dW[li].data_ptr(), o.ws.data_ptr(), o.ws_n, s)
         _lib.check("cg_fres_backward", st)
 
 
 FILTERS = ("chebyshev5", "fourier")
 
 
-def _net_sizes(filter, Fin, F, K, M, R, Fout_last):
-    """Parameter counts of one residual network's filters, in creation order."""
-    if filter == "fourier":
-        return _FourierResNet.sizes(Fin, F, M, R, Fout_last)
-    return _ResNet.sizes(Fin, F, K, R, Fout_last)
+def _net_class(filter):
+    if filter not in FILTERS:
+        raise ValueError(f"filter must be one of {FILTERS}, got {filter!r}")
+    return _FourierResNet if filter == "fourier" else _ResNet
 
 
-class _Trainer:
-    """Shared pieces of the explicit training schedules: flat parameter /
-    gradient / Adam buffers, the MSE loss with its moving average, the
-    exchange and the one Adam launch (lib/graph_model.py:246-310)."""
+class _ResModel(FlatTrainer):
+    """What ResGNN and StackedResGNN share: the graph (a Chebyshev plan, or U
+    prepared once for the transforms) and the flat Adam trainer over ``total``
+    parameters."""
 
-    def _setup(self, L, N, nfilter, K, nres_layer_count, Fout_last, learning_rate, decay_rate,
-               decay_steps, device, comm, lmax, total, filter="chebyshev5"):
-        self.device = torch.device(device if device is not None else "cuda")
-        dev_index = self.device.index if self.device.index is not None else 0
+    def __init__(self, L, N, nfilter, K, nres_layer_count, Fout_last, learning_rate, decay_rate,
+                 decay_steps, device, comm, lmax, filter, total):
+        super().__init__(total, (int(N), int(L.shape[0]), int(Fout_last)), "adam", learning_rate,
+                         decay_rate, decay_steps, device, comm)
         self.filter = filter
         if filter == "fourier":  # no Chebyshev plan: U, prepared once for the transforms
             self.plan = None
@@ -270,97 +267,17 @@ class _Trainer:
             self.U = _filter.fourier_basis(L, self.device)
             self.gft = ops.gft_prepare(self.U)
         else:
+            dev_index = self.device.index if self.device.index is not None else 0
             self.plan = plan_for(L, lmax=lmax, device=dev_index)
             self.M = self.plan.M
         self.N, self.nfilter, self.K = int(N), int(nfilter), int(K)
         self.R, self.Fout_last = int(nres_layer_count), int(Fout_last)
-        self.lr, self.decay_rate, self.decay_steps = learning_rate, decay_rate, decay_steps
-        self.comm = comm
-        f32 = dict(device=self.device, dtype=torch.float32)
-        self.flat = torch.empty(total, **f32)
-        self.grad = torch.zeros(total, **f32)
-        self.m = torch.zeros(total, **f32)
-        self.v = torch.zeros(total, **f32)
-        self.loss = torch.empty((1,), **f32)
-        # {biased, average, local_step} of ExponentialMovingAverage(0.9) of the loss
-        self.ema = torch.zeros((3,), **f32)
-        self.dout = torch.empty((self.N, self.M, self.Fout_last), **f32)
-        self.step_count = 0
-        nb = ctypes.c_size_t()
-        _lib.call("cg_mse_loss_workspace_bytes", self.N * self.M * self.Fout_last, ctypes.byref(nb))
-        self.mws = torch.empty(max(nb.value, 1), device=self.device, dtype=torch.uint8)
-        self.mws_n = nb.value
-        h = _lib.lib()
-        self._fwd, self._bwd, self._mse, self._adam = (h.cg_cheb_forward_layout,
-                                                       h.cg_cheb_backward_layout,
-                                                       h.cg_mse_loss_ema, h.cg_adam_update)
-        if filter == "fourier":
-            self._fwd, self._bwd = h.cg_fres_forward, h.cg_fres_backward
-        self._net = _FourierResNet if filter == "fourier" else _ResNet
 
-    def _alloc_ws(self, nets):
-        # one workspace serves every forward and backward call (stream order:
-        # a call's workspace is dead once the call has executed)
-        self.ws_n = max(n.ws_bytes() for n in nets)
-        self.ws = torch.empty(max(self.ws_n, 1), device=self.device, dtype=torch.uint8)
-
-    @property
-    def loss_average(self):
-        """The loss moving average (lib/graph_model.py:271-273), a device scalar."""
-        return self.ema[1:2]
-
-    def learning_rate(self, step):
-        """tf.train.exponential_decay(lr, global_step, decay_steps, decay_rate, staircase=True)."""
-        if self.decay_rate == 1 or not self.decay_steps:
-            return self.lr
-        return self.lr * self.decay_rate ** math.floor(step / self.decay_steps)
-
-    def _loss(self, out, labels, s):
-        n = out.numel()
-        labels = labels.contiguous()
-        if labels.numel() != n:
-            raise ValueError("labels must match the logits' shape")
-        _lib.check("cg_mse_loss_ema", self._mse(out.data_ptr(), labels.data_ptr(), n,
-                                                self.loss.data_ptr(), self.dout.data_ptr(),
-                                                self.ema.data_ptr(), ctypes.c_float(0.9),
-                                                self.mws.data_ptr(), self.mws_n, s))
-
-    def _exchange_and_update(self, s):
-        world = 1
-        if self.comm is not None and self.comm.world > 1:
-            self.comm.allreduce_sum_(self.grad, s)
-            world = self.comm.world
-        self.step_count += 1
-        lr = self.learning_rate(self.step_count - 1)
-        _lib.check("cg_adam_update", self._adam(
-            self.flat.data_ptr(), self.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
-            self.flat.numel(), ctypes.c_float(lr), ctypes.c_float(0.9), ctypes.c_float(0.999),
-            ctypes.c_float(1e-8), self.step_count, ctypes.c_float(1.0 / world), s))
-
-    def _stream(self, stream):
-        return stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream
-
-    def predict(self, data, labels=None):
-        """GraphModel.predict (lib/graph_model.py:64-94): predictions [size, M,
-        Fout_last] over batches of N, the last one zero-padded; with labels also
-        the reference's ``loss * batch_size / size`` (evaluate.predict has the
-        quirk).  No parameter, Adam slot, loss average or step count changes."""
-        from . import evaluate as _ev
-        return _ev.predict(self.forward, self.N, self.device, data, labels)
-
-    def evaluate(self, data, labels):
-        """GraphModel.evaluate (:96-122): (string, mse, 0, loss, predictions)."""
-        from . import evaluate as _ev
-        return _ev.evaluate(self.predict, data, labels)
-
-    def parameters(self):
-        return dict(zip(self.names, self.W))
-
-    def gradients(self):
-        return dict(zip(self.names, self.dW))
+    def _make_net(self, scope, Fin, gen):
+        return _net_class(self.filter)(self, scope, Fin, self.nfilter, self.K, self.R, self.Fout_last, gen)
 
 
-class ResGNN(_Trainer):
+class ResGNN(_ResModel):
     """ResGNN on one graph level (the fork's active model uses ``L[0]`` everywhere)."""
 
     def __init__(self, L, N: int, Fin: int, nfilter: int, K: int, nres_layer_count: int,
@@ -368,16 +285,15 @@ class ResGNN(_Trainer):
                  decay_steps: int | None = None, device=None, seed: int = 2017, comm=None,
                  lmax: float = 2, filter: str = "chebyshev5"):
         """filter: "chebyshev5" or "fourier" (K is then ignored, lib/graph_conv.py:103)."""
-        if filter not in FILTERS:
-            raise ValueError(f"filter must be one of {FILTERS}, got {filter!r}")
-        total = sum(_net_sizes(filter, Fin, nfilter, K, L.shape[0], nres_layer_count, Fout_last))
-        self._setup(L, N, nfilter, K, nres_layer_count, Fout_last, learning_rate, decay_rate,
-                    decay_steps, device, comm, lmax, total, filter)
+        total = sum(_net_class(filter).sizes(Fin, nfilter, K, L.shape[0], nres_layer_count, Fout_last))
+        super().__init__(L, N, nfilter, K, nres_layer_count, Fout_last, learning_rate, decay_rate,
+                         decay_steps, device, comm, lmax, filter, total)
         self.Fin = int(Fin)
         gen = torch.Generator(device=self.device)
         gen.manual_seed(seed)
-        self.net = self._net(self, "", self.Fin, 0, gen)
-        self.layers, self.names = self.net.layers, self.net.names
+        self.net = self._make_net("", self.Fin, gen)
+        self._carved()
+        self.layers = self.net.layers
         self.W, self.dW = self.net.W, self.net.dW
         # the forward's saved tensors: the Chebyshev bases, or the spectra xhat
         self.basis, self.out = getattr(self.net, "basis", None), self.net.out
@@ -400,7 +316,7 @@ class ResGNN(_Trainer):
         return self.loss
 
 
-class StackedResGNN(_Trainer):
+class StackedResGNN(_ResModel):
     """``GraphConv._inference`` with ``stack_num > 1`` (lib/graph_conv.py:272-303).
 
     ``groups`` are the channel ranges of the input fed to each residual
@@ -415,37 +331,28 @@ class StackedResGNN(_Trainer):
                  decay_rate: float = 0.95, decay_steps: int | None = None, device=None,
                  seed: int = 2017, comm=None, lmax: float = 2, filter: str = "chebyshev5"):
         """filter: "chebyshev5" or "fourier" (K is then ignored, lib/graph_conv.py:103)."""
-        if filter not in FILTERS:
-            raise ValueError(f"filter must be one of {FILTERS}, got {filter!r}")
+        net = _net_class(filter)
         groups = [(int(a), int(b)) for a, b in groups]
         if len(groups) < 1 or any(not (0 <= a < b <= C) for a, b in groups):
             raise ValueError(f"bad channel groups {groups} for C={C}")
         self.C, self.groups = int(C), groups
         M = L.shape[0]
-        sizes = [sum(_net_sizes(filter, b - a, nfilter, K, M, nres_layer_count, Fout_last))
-                 + M * Fout_last for a, b in groups]
-        self._setup(L, N, nfilter, K, nres_layer_count, Fout_last, learning_rate, decay_rate,
-                    decay_steps, device, comm, lmax, sum(sizes), filter)
+        total = sum(sum(net.sizes(b - a, nfilter, K, M, nres_layer_count, Fout_last)) + M * Fout_last
+                    for a, b in groups)
+        super().__init__(L, N, nfilter, K, nres_layer_count, Fout_last, learning_rate, decay_rate,
+                         decay_steps, device, comm, lmax, filter, total)
         gen = torch.Generator(device=self.device)
         gen.manual_seed(seed)
         f32 = dict(device=self.device, dtype=torch.float32)
         self.nets, self.merge_W, self.merge_dW = [], [], []
-        self.W, self.dW, self.names = [], [], []
-        off = 0
         for i, (a, b) in enumerate(groups):
-            net = self._net(self, f"final_merge/VC_{i}/", b - a, off, gen)
-            off = net.end
-            mf = self.M * self.Fout_last
-            w = self.flat[off:off + mf].view(self.M, self.Fout_last)
+            self.nets.append(self._make_net(f"final_merge/VC_{i}/", b - a, gen))
+            w, dw = self.carve((self.M, self.Fout_last), f"final_merge/W_{i}/weights")
             truncated_normal_(w, 0.1, gen)
-            dw = self.grad[off:off + mf].view(self.M, self.Fout_last)
-            off += mf
-            self.nets.append(net)
             self.merge_W.append(w)
             self.merge_dW.append(dw)
-            self.W += net.W + [w]
-            self.dW += net.dW + [dw]
-            self.names += net.names + [f"final_merge/W_{i}/weights"]
+        self._carved()
+        self.W, self.dW = self._tensors, self._grads
         self.x_groups = [torch.empty((self.N, self.M, b - a), **f32) if (a, b) != (0, self.C) else None
                          for a, b in groups]
         self.X = torch.empty((self.N, self.M, self.Fout_last), **f32)

@@ -1,0 +1,173 @@
+"""``FlatTrainer``: what the four device models (``ResGNN``, ``StackedResGNN``,
+``GLSTMModel``, ``GLSTMGconvModel``) share around their forward and backward
+passes (lib/graph_model.py:246-310; sgd / rmsprop of lib/gconvRNN.py:381-389).
+
+  buffers   every parameter is a view into ONE flat fp32 buffer (``flat``),
+            every gradient a view into ONE flat bucket (``grad``); the optimizer
+            slots ``s1`` / ``s2`` have the same size.  ``carve`` hands the views
+            out in creation order and records their names.
+  loss      mean((labels - out)^2), dout and the loss moving average
+            (lib/graph_model.py:265-273)                       cg_mse_loss_ema
+  exchange  ONE all-reduce(sum) of the bucket when ``comm.world`` > 1
+  update    ONE optimizer launch over ``flat``, grad_scale = 1/world, at the
+            staircase exponentially decayed learning rate
+  predict / evaluate  GraphModel's (lib/graph_model.py:64-122) through evaluate.py
+
+A model derives from it, allocates with ``FlatTrainer.__init__``, carves its
+parameters, calls ``_carved()`` and implements ``forward``.  ``comm`` is any
+object with ``allreduce_sum_(tensor, stream)`` and ``world`` (``dist.RcclComm``
+on RCCL, ``dist.TorchComm`` on a process group).
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+
+import torch
+
+from . import _lib
+from . import evaluate as _ev
+
+OPTIMIZERS = ("adam", "sgd", "rmsprop")
+
+
+class FlatTrainer:
+    OPTIMIZERS = OPTIMIZERS
+
+    def __init__(self, total: int, out_shape, optimizer: str, learning_rate, decay_rate, decay_steps,
+                 device, comm):
+        """total: the parameter count; out_shape: (N, M, Fout) of the model's output."""
+        if optimizer not in OPTIMIZERS:
+            raise ValueError(f"optimizer must be one of {OPTIMIZERS}")
+        self.device = torch.device(device if device is not None else "cuda")
+        self.optimizer, self.lr = optimizer, learning_rate
+        self.decay_rate, self.decay_steps = decay_rate, decay_steps
+        self.comm = comm
+        f32 = dict(device=self.device, dtype=torch.float32)
+        self.flat = torch.empty(total, **f32)
+        self.grad = torch.zeros(total, **f32)
+        # optimizer slots (TF 1.x: Adam m, v zeros; RMSProp ms ONES, mom zeros)
+        self.s1 = (torch.ones if optimizer == "rmsprop" else torch.zeros)(total, **f32)
+        self.s2 = torch.zeros(total, **f32)
+        self.loss = torch.empty((1,), **f32)
+        # {biased, average, local_step} of ExponentialMovingAverage(0.9) of the loss
+        self.ema = torch.zeros((3,), **f32)
+        self.dout = torch.empty(tuple(out_shape), **f32)
+        nb = ctypes.c_size_t()
+        _lib.call("cg_mse_loss_workspace_bytes", math.prod(out_shape), ctypes.byref(nb))
+        self.mws = torch.empty(max(nb.value, 1), device=self.device, dtype=torch.uint8)
+        self.mws_n = nb.value
+        self.step_count = 0
+        # names / tensors / gradient views in carving order; ``params``: the
+        # autograd-owned ones (torch.nn.Parameter, .grad = the bucket view)
+        self.names, self.params = [], []
+        self._tensors, self._grads, self._off = [], [], 0
+        h = _lib.lib()  # the step's C entry points, looked up once
+        self._mse = h.cg_mse_loss_ema
+        self._update = {"adam": h.cg_adam_update, "sgd": h.cg_sgd_update,
+                        "rmsprop": h.cg_rmsprop_update}[optimizer]
+
+    # -- carving ------------------------------------------------------------------
+    def carve(self, shape, name: str, init=None):
+        """The next (parameter view, gradient view) of ``shape`` in the flat
+        buffers.  With ``init`` (the LSTM cells, autograd-owned): ``init`` is
+        copied in and the first is a ``torch.nn.Parameter`` aliasing ``flat``
+        whose ``.grad`` is the bucket view."""
+        n = math.prod(shape)
+        w = self.flat[self._off:self._off + n].view(shape)
+        g = self.grad[self._off:self._off + n].view(shape)
+        if init is not None:
+            with torch.no_grad():
+                w.copy_(init)
+            w = torch.nn.Parameter(w)
+            w.grad = g
+            self.params.append(w)
+        self._off += n
+        self.names.append(name)
+        self._tensors.append(w)
+        self._grads.append(g)
+        return w, g
+
+    def _carved(self):
+        assert self._off == self.flat.numel(), (self._off, self.flat.numel())
+
+    def _alloc_ws(self, nets):
+        # one workspace serves every forward and backward call of the nets (stream
+        # order: a call's workspace is dead once the call has executed)
+        self.ws_n = max(n.ws_bytes() for n in nets)
+        self.ws = torch.empty(max(self.ws_n, 1), device=self.device, dtype=torch.uint8)
+
+    def parameters(self):
+        return dict(zip(self.names, self._tensors))
+
+    def gradients(self):
+        return dict(zip(self.names, (g if t.grad is None else t.grad
+                                     for t, g in zip(self._tensors, self._grads))))
+
+    # -- the step's shared pieces -----------------------------------------------------
+    @property
+    def world(self):
+        return self.comm.world if self.comm is not None else 1
+
+    @property
+    def loss_average(self):
+        """The loss moving average (lib/graph_model.py:271-273), a device scalar."""
+        return self.ema[1:2]
+
+    def learning_rate(self, step):
+        """tf.train.exponential_decay(lr, global_step, decay_steps, decay_rate, staircase=True)."""
+        if self.decay_rate == 1 or not self.decay_steps:
+            return self.lr
+        return self.lr * self.decay_rate ** math.floor(step / self.decay_steps)
+
+    def _stream(self, stream):
+        return stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream
+
+    def _loss(self, out, labels, s):
+        """loss, dout and the moving average from the logits; ``self.dout`` feeds the backward."""
+        n = out.numel()
+        labels = labels.contiguous()
+        if labels.numel() != n:
+            raise ValueError("labels must match the logits' shape")
+        _lib.check("cg_mse_loss_ema", self._mse(out.data_ptr(), labels.data_ptr(), n,
+                                                self.loss.data_ptr(), self.dout.data_ptr(),
+                                                self.ema.data_ptr(), ctypes.c_float(0.9),
+                                                self.mws.data_ptr(), self.mws_n, s))
+
+    def _exchange_and_update(self, s):
+        """The tail of a step: every autograd-owned .grad still inside the bucket,
+        ONE all-reduce when world > 1, ONE optimizer launch with grad_scale = 1/world."""
+        lo = self.grad.data_ptr()
+        for p in self.params:  # autograd accumulated into the flat bucket in place
+            if p.grad is None or not lo <= p.grad.data_ptr() < lo + 4 * self.grad.numel():
+                raise RuntimeError("a parameter's .grad left the flat gradient bucket")
+        world = self.world
+        if world > 1:
+            self.comm.allreduce_sum_(self.grad, s)
+        self.step_count += 1
+        f = ctypes.c_float
+        flat, grad, n = self.flat.data_ptr(), self.grad.data_ptr(), self.flat.numel()
+        lr, scale = f(self.learning_rate(self.step_count - 1)), f(1.0 / world)
+        if self.optimizer == "adam":
+            st = self._update(flat, grad, self.s1.data_ptr(), self.s2.data_ptr(), n, lr, f(0.9),
+                              f(0.999), f(1e-8), self.step_count, scale, s)
+        elif self.optimizer == "sgd":
+            st = self._update(flat, grad, n, lr, scale, s)
+        else:
+            st = self._update(flat, grad, self.s1.data_ptr(), self.s2.data_ptr(), n, lr, f(0.9),
+                              f(0.0), f(1e-10), scale, s)
+        _lib.check(f"cg_{self.optimizer}_update", st)
+
+    # -- inference ------------------------------------------------------------------
+    def predict(self, data, labels=None, **forward_kw):
+        """GraphModel.predict (lib/graph_model.py:64-94): predictions [size, M,
+        Fout] over batches of N, the last one zero-padded; with labels also the
+        reference's ``loss * batch_size / size`` (evaluate.predict has the quirk,
+        padded rows included).  ``forward_kw`` goes to the model's ``forward``.
+        No parameter, optimizer slot, loss average or step count changes."""
+        fwd = (lambda b: self.forward(b, **forward_kw)) if forward_kw else self.forward
+        return _ev.predict(fwd, self.N, self.device, data, labels)
+
+    def evaluate(self, data, labels, **forward_kw):
+        """GraphModel.evaluate (:96-122): (string, mse, 0, loss, predictions)."""
+        return _ev.evaluate(lambda d, l: FlatTrainer.predict(self, d, l, **forward_kw), data, labels)

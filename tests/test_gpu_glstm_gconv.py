@@ -320,28 +320,54 @@ def test_adam_step_matches_reference(dev, filter, seam):
         assert not np.array_equal(npy(p), p0.astype(np.float32)), name
 
 
+MODELS = ["GLSTMGconvModel", "GLSTMModel", "ResGNN", "StackedResGNN"]
+
+
+def _build(dev, which, **kw):
+    """One of the four model classes at the small shapes; each reads x [3, 40, 6]."""
+    from cnn_graph_amd.gconv_lstm import GLSTMModel
+    from cnn_graph_amd.model import ResGNN, StackedResGNN
+    L = laplacian("40")
+    if which == "GLSTMGconvModel":
+        return make_model(dev, "fourier_conv", 40, 3, 3, 2, 8, 8, 2, 1, 2, 0.8, "fused", **kw)[0]
+    if which == "GLSTMModel":
+        return GLSTMModel(L, 3, 3, 2, num_hidden=8, K=2, layer_count=2, out_features=2, keep_prob=0.8,
+                          device=dev, seed=5, **kw)
+    if which == "ResGNN":
+        return ResGNN(L, 3, 6, 8, 3, 1, 2, device=dev, seed=5, **kw)
+    return StackedResGNN(L, 3, 6, 8, 3, 1, groups=((0, 4), (4, 6)), device=dev, seed=5, filter="fourier",
+                         **kw)
+
+
 class _DoublingComm:
     """world 2 with both ranks holding the same gradient: the sum is 2 g."""
     world, rank = 2, 0
 
     def __init__(self):
-        self.calls = 0
+        self.calls = []
 
     def allreduce_sum_(self, tensor, stream):
-        self.calls += 1
+        self.calls.append((tensor.data_ptr(), tensor.numel()))
         tensor.mul_(2.0)
 
 
-def test_comm_contract_one_allreduce_and_grad_scale(dev):
+@pytest.mark.parametrize("which", MODELS)
+def test_comm_contract_one_allreduce_and_grad_scale(dev, which):
     comm = _DoublingComm()
-    a, _ = make_model(dev, "fourier_conv", 40, 3, 3, 2, 8, 8, 2, 1, 1, 0.8, "fused")
-    b, _ = make_model(dev, "fourier_conv", 40, 3, 3, 2, 8, 8, 2, 1, 1, 0.8, "fused", comm=comm)
-    x, labels = _batch(a)
+    a, b = _build(dev, which), _build(dev, which, comm=comm)
+    rng = np.random.default_rng(3)
+    x = r32(0.5 * rng.standard_normal((3, 40, 6)))
+    labels = r32(rng.standard_normal((3, 40, 2)))
+    assert torch.equal(a.flat, b.flat)
+    start = a.flat.clone()
     for m in (a, b):
         m.train_step(t(x, dev), t(labels, dev))
     torch.cuda.synchronize()
-    assert comm.calls == 1 and b.world == 2
+    # exactly one all-reduce, of the whole bucket
+    assert comm.calls == [(b.grad.data_ptr(), b.grad.numel())] and b.world == 2 and a.world == 1
+    assert b.grad.numel() == b.flat.numel()
     assert torch.equal(a.flat, b.flat)  # (2 g) * 1/2 is exact
+    assert not torch.equal(a.flat, start)
 
 
 @pytest.mark.parametrize("optimizer", ["sgd", "rmsprop"])
@@ -359,35 +385,21 @@ def test_other_optimizers_step(dev, optimizer):
 
 
 # ===== e. predict and evaluate ===================================================================
-def _models_for_predict(dev):
-    from cnn_graph_amd.gconv_lstm import GLSTMModel
-    from cnn_graph_amd.model import ResGNN, StackedResGNN
-    L = laplacian("40")
-    gg, _ = make_model(dev, "fourier_conv", 40, 3, 3, 2, 8, 8, 2, 1, 2, 0.8, "fused")
-    gl = GLSTMModel(L, 3, 3, 2, num_hidden=8, K=2, layer_count=2, out_features=2, keep_prob=0.8,
-                    device=dev, seed=5)
-    rg = ResGNN(L, 3, 6, 8, 3, 1, 2, device=dev, seed=5)
-    sg = StackedResGNN(L, 3, 6, 8, 3, 1, groups=((0, 4), (4, 6)), device=dev, seed=5, filter="fourier")
-    def glstm_plain(m, b):  # GLSTMModel.forward with every layer unwrapped
-        wrapped, m.wrapped = m.wrapped, m.cells
-        try:
-            return m.forward(b)
-        finally:
-            m.wrapped = wrapped
-
-    return {"GLSTMGconvModel": (gg, lambda m, b: m.forward(b, dropout=False)),
-            "GLSTMModel": (gl, glstm_plain), "ResGNN": (rg, lambda m, b: m.forward(b)),
-            "StackedResGNN": (sg, lambda m, b: m.forward(b))}
+_plain = lambda m, b: m.forward(b)  # noqa: E731
+_undropped = lambda m, b: m.forward(b, dropout=False)  # noqa: E731
+# the per-batch forward that predict's default (no dropout) must equal bitwise
+_PREDICT_FORWARD = {"GLSTMGconvModel": _undropped, "GLSTMModel": _undropped, "ResGNN": _plain,
+                    "StackedResGNN": _plain}
 
 
 def _state(m):
-    slots = [m.flat, m.ema] + [getattr(m, n) for n in ("s1", "s2", "m", "v") if hasattr(m, n)]
+    slots = [m.flat, m.ema, m.s1, m.s2]
     return [s.clone() for s in slots], m.step_count
 
 
-@pytest.mark.parametrize("which", ["GLSTMGconvModel", "GLSTMModel", "ResGNN", "StackedResGNN"])
+@pytest.mark.parametrize("which", MODELS)
 def test_predict_and_evaluate(dev, which):
-    m, fwd = _models_for_predict(dev)[which]
+    m, fwd = _build(dev, which), _PREDICT_FORWARD[which]
     N, M = m.N, m.M
     size = 2 * N + 1
     rng = np.random.default_rng(17)
@@ -454,3 +466,27 @@ def test_resgnn_unchanged(dev, filter):
     assert np.array_equal(flat, gold[f"{filter}_flat"])
     assert np.array_equal(loss, gold[f"{filter}_loss"])
     assert os.path.getsize(os.path.join(GOLDEN, "resgnn_steps.npz")) < (1 << 20)
+
+
+# ===== g. the other three models unchanged =====================================================
+def _golden_steps():
+    sys.path.insert(0, GOLDEN)
+    try:
+        import make_resgnn_steps as G
+    finally:
+        sys.path.remove(GOLDEN)
+    return G
+
+
+@pytest.mark.parametrize("name", list(_golden_steps().MODEL_CASES))
+def test_models_unchanged(dev, name):
+    """tests/golden/model_steps.npz holds flat, loss and the loss moving average of
+    StackedResGNN, GLSTMModel and GLSTMGconvModel after two train_steps (the second
+    at the decayed learning rate) as the commit before trainer.FlatTrainer computed
+    them (tests/golden/make_resgnn_steps.py --models)."""
+    gold = load_golden("model_steps.npz")
+    flat, loss, ema = _golden_steps().run_model_steps(name)
+    assert np.array_equal(flat, gold[f"{name}_flat"])
+    assert np.array_equal(loss, gold[f"{name}_loss"])
+    assert np.array_equal(ema, gold[f"{name}_ema"])
+    assert os.path.getsize(os.path.join(GOLDEN, "model_steps.npz")) < (1 << 20)
