@@ -144,6 +144,10 @@ _SIGNATURES = {
     "cg_dropout_forward": ([_vp, ctypes.c_int64, ctypes.c_float, ctypes.c_uint64, _vp, _vp], _c_int),
     "cg_dropout_backward": ([_vp, ctypes.c_int64, ctypes.c_float, ctypes.c_uint64, _vp, _vp], _c_int),
     "cg_clip_by_norm": ([_vp, ctypes.c_int64, ctypes.c_float, _vp, _vp], _c_int),
+    "cg_seq_xent_workspace_bytes": ([_c_i32, _c_i32, _c_i32, _c_i32, ctypes.POINTER(_c_sz)], _c_int),
+    "cg_seq_xent_head": ([_vp, _vp, _vp, _vp, _c_i32, _c_i32, _c_i32, _c_i32, ctypes.c_float,
+                          ctypes.c_uint64, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_sz,
+                          _vp], _c_int),
     "cg_lstm_seq_x_supported": ([_vp, _c_i32, _c_i32, _c_i32, ctypes.POINTER(_c_i32)], _c_int),
     "cg_lstm_seq_forward_x": ([_vp, _c_i32, _c_i32, _c_i32, _c_i32, _c_i32, _c_i32, _vp, _vp, _vp,
                                _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _c_sz,

@@ -447,6 +447,15 @@ hipError_t launch_clip_norm(float* t, int64_t n, float c, int* nonfinite, hipStr
 hipError_t launch_stack_merge_bwd(const float* dy, const float* o, const float* w, int N, int64_t MF,
                                   float* d_o, float* dw, hipStream_t s);
 
+// ---- per-step output head + vertex softmax cross-entropy (seq_xent.hip) -----------
+// hs [T][N][M][H], labels [T][N]; ws: seq_xent_ws_bytes.  dhs NULL = forward
+// only (dw, db unused); logits ([N][M][T]) and ce ([T][N]) nullable.  H <= 256.
+size_t seq_xent_ws_bytes(int64_t P, int M, int H);
+hipError_t launch_seq_xent(const float* hs, const float* w, const float* b, const int32_t* labels,
+                           int T, int N, int M, int H, float keep, unsigned long long seed,
+                           float loss_scale, float* logits, float* ce, float* loss, float* dhs,
+                           float* dw, float* db, float* ws, hipStream_t s);
+
 // ---- gconv-LSTM cell (lstm.hip) ------------------------------------------------
 // gates: 0 = reference gate functions (tan / sigmoid / sigmoid / tanh,
 // lib/gconv_lstm.py:188-209), 1 = standard LSTM (tanh / ... / sigmoid).

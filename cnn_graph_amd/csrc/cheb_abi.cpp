@@ -1323,6 +1323,34 @@ int cg_clip_by_norm(float* t, int64_t n, float clip_norm, int32_t* nonfinite, vo
   return ok();
 }
 
+int cg_seq_xent_workspace_bytes(int32_t T, int32_t N, int32_t M, int32_t H, size_t* out) {
+  if (!out || T < 1 || N < 1 || M < 1 || H < 1 || int64_t(T) * N > INT32_MAX)
+    return fail(CG_ERR_ARG, "seq_xent_workspace_bytes: bad arguments");
+  if (H > 256) return fail(CG_ERR_UNSUPPORTED, "seq_xent: H = %d, the head supports H <= 256", H);
+  *out = al256(cg::seq_xent_ws_bytes(int64_t(T) * N, M, H));
+  return ok();
+}
+
+int cg_seq_xent_head(const float* hs, const float* w, const float* b, const int32_t* labels,
+                     int32_t T, int32_t N, int32_t M, int32_t H, float keep, uint64_t seed,
+                     float loss_scale, float* logits, float* ce, float* loss, float* dhs, float* dw,
+                     float* db, void* ws, size_t ws_bytes, void* stream) {
+  if (!hs || !w || !b || !labels || !loss || (dhs && (!dw || !db)))
+    return fail(CG_ERR_ARG, "seq_xent_head: null pointer");
+  if (T < 1 || N < 1 || M < 1 || H < 1 || int64_t(T) * N > INT32_MAX)
+    return fail(CG_ERR_ARG, "seq_xent_head: bad sizes (T=%d N=%d M=%d H=%d)", T, N, M, H);
+  if (!(keep > 0.f && keep <= 1.f))
+    return fail(CG_ERR_ARG, "seq_xent_head: keep = %g outside (0, 1]", keep);
+  if (H > 256) return fail(CG_ERR_UNSUPPORTED, "seq_xent: H = %d, the head supports H <= 256", H);
+  const size_t need = al256(cg::seq_xent_ws_bytes(int64_t(T) * N, M, H));
+  if (!ws || ws_bytes < need)
+    return fail(CG_ERR_ARG, "seq_xent_head workspace too small: %zu < %zu", ws_bytes, need);
+  CG_HIP(cg::launch_seq_xent(hs, w, b, labels, T, N, M, H, keep, seed, loss_scale, logits, ce, loss,
+                             dhs, dw, db, static_cast<float*>(ws),
+                             reinterpret_cast<hipStream_t>(stream)));
+  return ok();
+}
+
 int cg_slice_channels(const float* x, int64_t rows, int32_t C, int32_t c0, int32_t c1, float* out,
                       void* stream) {
   if (!x || !out || rows < 1 || C < 1 || c0 < 0 || c1 <= c0 || c1 > C)

@@ -772,7 +772,7 @@ class LSTMStackTrainer(FlatTrainer):
 
     def __init__(self, L, N, T, feat_in, num_hidden, K, layer_count, out_features, keep_prob, filter,
                  tail_numel, optimizer, learning_rate, decay_rate, decay_steps, lmax, gates, device,
-                 seed, comm):
+                 seed, comm, hconv="auto"):
         if filter not in ("cheby_conv", "fourier_conv"):
             raise ValueError("filter must be 'cheby_conv' or 'fourier_conv'")
         self.filter = filter
@@ -783,7 +783,8 @@ class LSTMStackTrainer(FlatTrainer):
         gen.manual_seed(seed)
         cells = [GConvLSTMCell(self.H, laplacian=L, lmax=lmax, K=self.K,
                                feat_in=self.F if li == 0 else self.H, gates=gates, device=device,
-                               generator=gen, filter_type=filter) for li in range(int(layer_count))]
+                               generator=gen, filter_type=filter, hconv=hconv)
+                 for li in range(int(layer_count))]
         self.M = cells[0]._nNode
         super().__init__(sum(p.numel() for c in cells for p in c.parameters()) + tail_numel,
                          (self.N, self.M, self.Fout), optimizer, learning_rate, decay_rate, decay_steps,

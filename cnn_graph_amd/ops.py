@@ -17,8 +17,10 @@ or a missing library raises.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -871,6 +873,113 @@ def clip_by_norm_(grads, clip_norm: float, check_numerics: bool = True):
     if check_numerics and flag is not None and int(flag.item()):
         raise FloatingPointError("Numerical error in gradient (check_numerics after clip_by_norm)")
     return grads
+
+
+# -- the per-step output head + vertex softmax loss (lib/gconvRNN.py:306-340) -------
+SeqXent = collections.namedtuple("SeqXent", ("loss", "logits", "ce", "dhs", "dw", "db"))
+
+
+def seq_xent_labels(labels, M: int, device) -> torch.Tensor:
+    """Step-major labels [T, N] as the int32 device tensor cg_seq_xent_head
+    reads.  Host labels (numpy, lists, CPU tensors) are validated against [0, M)
+    before the upload (ValueError); a device tensor is taken as it is -- an
+    out-of-range entry then gives that pair NaN, as TF's GPU kernel does."""
+    if isinstance(labels, torch.Tensor) and labels.is_cuda:
+        return labels.to(dtype=torch.int32).contiguous()
+    a = np.asarray(labels.numpy() if isinstance(labels, torch.Tensor) else labels)
+    if a.dtype.kind not in "iu":
+        raise TypeError(f"labels must be integers, got {a.dtype}")
+    if a.size and (a.min() < 0 or a.max() >= M):
+        raise ValueError(f"labels must lie in [0, {M}), got [{a.min()}, {a.max()}]")
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(device)
+
+
+def seq_xent_workspace_bytes(T: int, N: int, M: int, H: int) -> int:
+    nb = ctypes.c_size_t()
+    _lib.call("cg_seq_xent_workspace_bytes", int(T), int(N), int(M), int(H), ctypes.byref(nb))
+    return nb.value
+
+
+def seq_xent_call(hs, w, b, labels, keep: float = 1.0, seed: int = 0, loss_scale: float = 1.0,
+                  need_grad: bool = True, want_logits: bool = False, want_ce: bool = False,
+                  ws=None, out_dhs=None, out_dw=None, out_db=None) -> SeqXent:
+    """cg_seq_xent_head on hs [T, N, M, H], w [H] (or [H, 1]), b [1], labels
+    [T, N] (seq_xent_labels): one pass gives loss [1] = loss_scale * sum ce and,
+    with need_grad, dhs, dw [H], db [1]; logits [N, M, T] (pred_out) and ce
+    [T, N] on request.  keep < 1 folds DropoutWrapper's mask of stream ``seed``
+    (already offset) into the read of hs and the write of dhs."""
+    _check_dev("hs", hs)
+    _check_dev("w", w)
+    _check_dev("b", b)
+    _check_dev("labels", labels, torch.int32)
+    if hs.dim() != 4:
+        raise ValueError("hs must be [T, N, M, H]")
+    T, N, M, H = (int(d) for d in hs.shape)
+    if w.numel() != H or b.numel() != 1 or tuple(labels.shape) != (T, N):
+        raise ValueError(f"need w [{H}], b [1] and labels [{T}, {N}]")
+    hs, w, labels = hs.contiguous(), w.contiguous(), labels.contiguous()
+    f32 = dict(device=hs.device, dtype=torch.float32)
+    nb = seq_xent_workspace_bytes(T, N, M, H)
+    if ws is None:
+        ws = torch.empty(nb, device=hs.device, dtype=torch.uint8)
+    loss = torch.empty((1,), **f32)
+    logits = torch.empty((N, M, T), **f32) if want_logits else None
+    ce = torch.empty((T, N), **f32) if want_ce else None
+    dhs = dw = db = None
+    if need_grad:
+        dhs = out_dhs if out_dhs is not None else torch.empty_like(hs)
+        dw = out_dw if out_dw is not None else torch.empty((H,), **f32)
+        db = out_db if out_db is not None else torch.empty((1,), **f32)
+        _check_out("out_dhs", dhs, hs.shape)
+        _check_out("out_dw", dw, (H,))
+        _check_out("out_db", db, (1,))
+    _lib.call("cg_seq_xent_head", _p(hs), _p(w), _p(b), _p(labels), T, N, M, H, float(keep),
+              int(seed) & ((1 << 64) - 1), float(loss_scale), _p(logits), _p(ce), _p(loss), _p(dhs),
+              _p(dw), _p(db), _p(ws), ws.numel(), _stream(hs))
+    return SeqXent(loss, logits, ce, dhs, dw, db)
+
+
+class _SeqXentHead(torch.autograd.Function):
+    """loss (and pred_out) of the head; the gradients are computed by the same
+    launch and handed out, times the incoming scalar, in the backward (as the
+    trainer uses cg_mse_loss_ema's dpred)."""
+
+    @staticmethod
+    def forward(ctx, hs, w, b, labels, keep, seed, loss_scale, want_logits):
+        need = any(ctx.needs_input_grad[:3])
+        r = seq_xent_call(hs, w.reshape(-1), b, labels, keep, seed, loss_scale, need_grad=need,
+                          want_logits=want_logits)
+        ctx.w_shape = tuple(w.shape)
+        if need:
+            ctx.save_for_backward(r.dhs, r.dw, r.db)
+        logits = r.logits if want_logits else hs.new_empty(0)
+        ctx.mark_non_differentiable(logits)
+        return r.loss, logits
+
+    @staticmethod
+    def backward(ctx, dloss, _dlogits):
+        dhs, dw, db = ctx.saved_tensors
+        n = ctx.needs_input_grad
+        return (dhs * dloss if n[0] else None, (dw * dloss).view(ctx.w_shape) if n[1] else None,
+                db * dloss if n[2] else None, None, None, None, None, None)
+
+
+def seq_xent_head(hs, w, b, labels, mask=None, loss_scale: float = 1.0, want_logits: bool = False):
+    """The gconvRNN output head and loss (lib/gconvRNN.py:306-340) on hs
+    [T, N, M, H]: logits[t, n, m] = hd[t, n, m, :] . w + b over hd = hs through
+    ``mask`` = (keep_prob, seed) -- DropoutWrapper's mask, seed already offset --
+    or hs itself; loss [1] = loss_scale * sum_{t,n} sparse_softmax_cross_entropy
+    (logits[t, n, :], labels[t, n]).  labels [T, N]: host integers (validated
+    against [0, M)) or an int32 device tensor.  Returns loss, or (loss, pred_out
+    [N, M, T]) with want_logits.  With gradients disabled the launch is the
+    forward-only one (dhs = NULL)."""
+    _check_dev("hs", hs)
+    labels = seq_xent_labels(labels, int(hs.shape[2]), hs.device)
+    keep, seed = (1.0, 0) if mask is None else (float(mask[0]), int(mask[1]))
+    _check_keep(keep)
+    loss, logits = _SeqXentHead.apply(hs, w, b, labels, keep, seed, float(loss_scale),
+                                      bool(want_logits))
+    return (loss, logits) if want_logits else loss
 
 
 def adam_update(param, grad, m, v, step: int, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8,

@@ -9,8 +9,9 @@ passes (lib/graph_model.py:246-310; sgd / rmsprop of lib/gconvRNN.py:381-389).
   loss      mean((labels - out)^2), dout and the loss moving average
             (lib/graph_model.py:265-273)                       cg_mse_loss_ema
   exchange  ONE all-reduce(sum) of the bucket when ``comm.world`` > 1
-  update    ONE optimizer launch over ``flat``, grad_scale = 1/world, at the
-            staircase exponentially decayed learning rate
+  update    ONE optimizer launch over ``flat``, grad_scale = 1/world
+            (``_grad_scale``), at the staircase exponentially decayed learning
+            rate; ``_after_exchange`` runs between exchange and update
   predict / evaluate  GraphModel's (lib/graph_model.py:64-122) through evaluate.py
 
 A model derives from it, allocates with ``FlatTrainer.__init__``, carves its
@@ -134,6 +135,15 @@ class FlatTrainer:
                                                 self.ema.data_ptr(), ctypes.c_float(0.9),
                                                 self.mws.data_ptr(), self.mws_n, s))
 
+    # two hooks of the step's tail; the defaults are the mean-loss models'
+    def _grad_scale(self, world: int) -> float:
+        """What the optimizer multiplies the exchanged (summed) bucket by: 1/world
+        for a loss that is a mean over the batch."""
+        return 1.0 / world
+
+    def _after_exchange(self, s):
+        """Called between the all-reduce and the optimizer launch (gradient clipping)."""
+
     def _exchange_and_update(self, s):
         """The tail of a step: every autograd-owned .grad still inside the bucket,
         ONE all-reduce when world > 1, ONE optimizer launch with grad_scale = 1/world."""
@@ -144,10 +154,11 @@ class FlatTrainer:
         world = self.world
         if world > 1:
             self.comm.allreduce_sum_(self.grad, s)
+        self._after_exchange(s)
         self.step_count += 1
         f = ctypes.c_float
         flat, grad, n = self.flat.data_ptr(), self.grad.data_ptr(), self.flat.numel()
-        lr, scale = f(self.learning_rate(self.step_count - 1)), f(1.0 / world)
+        lr, scale = f(self.learning_rate(self.step_count - 1)), f(self._grad_scale(world))
         if self.optimizer == "adam":
             st = self._update(flat, grad, self.s1.data_ptr(), self.s2.data_ptr(), n, lr, f(0.9),
                               f(0.999), f(1e-8), self.step_count, scale, s)

@@ -606,6 +606,38 @@ int cg_dropout_backward(const float* dy, int64_t n, float keep_prob, uint64_t se
 int cg_clip_by_norm(float* t, int64_t n, float clip_norm, int32_t* nonfinite, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * cg_seq_xent_head: the per-step output head of the structured-sequence
+ * gconv-LSTM (lib/gconvRNN.py:306-317) with its softmax cross-entropy over the
+ * vertices (sparse_softmax_cross_entropy_with_logits, :326-340), forward and
+ * backward in one pass over hs [T][N][M][H].  For every pair (t, n):
+ *   hd[m,:]   = hs[t,n,m,:] through the DropoutWrapper's mask (keep < 1: the
+ *               arithmetic of cg_dropout_forward on element e = the flat index
+ *               in [T][N][M][H]; seed already offset as for cg_dropout_forward)
+ *   logit[m]  = hd[m,:] . w + b                    w [H], b [1]
+ *   ce[t,n]   = max + log sum_m exp(logit[m] - max) - logit[labels[t,n]]
+ *   dlogit[m] = loss_scale (exp(logit[m] - lse) - [m == label])
+ *   dw = sum dlogit[m] hd[m,:], db = sum dlogit[m]  (over every pair and vertex)
+ *   dhs[t,n,m,:] = dlogit[m] w through the mask's backward form
+ *   loss      = loss_scale * sum_{t,n} ce[t,n]
+ * so head(hs, keep, seed) is bit for bit head(cg_dropout_forward(hs), keep = 1)
+ * and its dhs the cg_dropout_backward of that call's.  logits ([N][M][T], the
+ * reference's pred_out) and ce ([T][N]) are optional outputs; dhs NULL is the
+ * forward-only call (dw, db unused), else dw [H] and db [1] are required.  All
+ * sums run in a fixed order (per-pair partials in the workspace, then one small
+ * reduction launch; no atomics): repeated calls agree bitwise.  A label outside
+ * [0, M) is not used as an index: that pair's ce, dhs and so dw, db and loss
+ * are NaN.  Any M >= 1, 1 <= H <= 256 (H > 256: CG_ERR_UNSUPPORTED); dwordx4
+ * accesses when H % 4 == 0 and hs, dhs are 16-byte aligned.  Null required
+ * pointers, non-positive sizes, keep outside (0, 1] and a workspace smaller
+ * than cg_seq_xent_workspace_bytes return CG_ERR_ARG before any device work.
+ * ------------------------------------------------------------------------- */
+int cg_seq_xent_workspace_bytes(int32_t T, int32_t N, int32_t M, int32_t H, size_t* out);
+int cg_seq_xent_head(const float* hs, const float* w, const float* b, const int32_t* labels,
+                     int32_t T, int32_t N, int32_t M, int32_t H, float keep, uint64_t seed,
+                     float loss_scale, float* logits, float* ce, float* loss, float* dhs, float* dw,
+                     float* db, void* ws, size_t ws_bytes, void* hip_stream);
+
+/* ---------------------------------------------------------------------------
  * perm_data (lib/coarsening.py:219-240) on device:
  *   out[n][i][f] = perm[i] < M_in ? x[n][perm[i]][f] : 0   (fake vertices are 0)
  * x [N][M_in][F], perm [M_out] (int32), out [N][M_out][F].

@@ -11,6 +11,9 @@
   RF  the ResGNN training step with the Fourier filter at the reference's published shape
       (M=1024, batch 100, 10 channels, nfilter 32, 4 residual layers) against forward +
       backward of the same network on the older unfused ops under autograd
+  S   the gconvRNN sequence model at config E's graph and shape (T=12, N=128, Fin=2, H=32,
+      K=3, keep 0.8): the fused per-step softmax head against its composition from
+      ops.dropout and torch ops, and the training step with each seam
 
 fwd / bwd are HIP-event timings (torch's current stream, where every C-ABI
 call is enqueued) of one chebyshev5 forward and backward (dx + dW), median of
@@ -18,7 +21,7 @@ rounds; alg_GBps uses SURVEY.md §8d's algorithmic bytes.  Each line carries a
 `cpu_baseline`: the oracle's fwd+bwd of the same config on the host cores
 (bench.py's CPU legs -- the only place outside tests/ that runs oracle/),
 median of the timed passes, with the sub-batch and pass count stated.
-Usage: python scripts/bench_configs.py [A C1 C2 D E EF R RF] [--d-batch N] [--layout auto|rows|planes]
+Usage: python scripts/bench_configs.py [A C1 C2 D E EF R RF S] [--d-batch N] [--layout auto|rows|planes]
                                        [--no-cpu] [--cpu-seconds S]
 """
 from __future__ import annotations
@@ -387,6 +390,84 @@ def glstm_gconv_config(dev, filter="fourier_conv", T=6, N=50, Fin=2, H=128, C=32
     return out
 
 
+def seq_head_config(dev, T=12, N=128, Fin=2, H=32, K=3, keep=0.8, runs=5):
+    """S: the gconvRNN sequence model (gconv_rnn.GConvRNNModel) at config E's
+    graph and shape.  (a) the fused head (cg_seq_xent_head: mask, logits,
+    softmax loss and every gradient in one pass over hs [T, N, M, H]) against
+    the same math composed from ops.dropout and torch's matmul / log_softmax /
+    autograd -- the baseline; (b) one training step with each seam.  HIP events,
+    the variants interleaved run by run; per-run numbers, medians and the
+    unfused range that ``seam="auto"`` is decided on."""
+    from cnn_graph_amd.gconv_rnn import GConvRNNModel
+    _, L = graph_e()
+    M = L.shape[0]
+    g = torch.Generator(device=dev)
+    g.manual_seed(7)
+    hs = torch.randn((T, N, M, H), device=dev, generator=g).requires_grad_()
+    w = torch.randn((H, 1), device=dev, generator=g).requires_grad_()
+    b = torch.randn((1,), device=dev, generator=g).requires_grad_()
+    lab_host = np.random.default_rng(7).integers(0, M, (T, N))
+    lab = ops.seq_xent_labels(lab_host, M, dev)
+    lab64 = lab.long()
+    seed, scale = 0x5EED, 1.0 / T
+    ws = torch.empty(ops.seq_xent_workspace_bytes(T, N, M, H), device=dev, dtype=torch.uint8)
+    dhs, dw, db = torch.empty_like(hs), torch.empty((H,), device=dev), torch.empty((1,), device=dev)
+
+    def fused():
+        return ops.seq_xent_call(hs.detach(), w.detach(), b.detach(), lab, keep, seed, scale, ws=ws,
+                                 out_dhs=dhs, out_dw=dw, out_db=db)
+
+    def composed():
+        for p in (hs, w, b):
+            p.grad = None
+        logits = (ops.dropout(hs, keep, seed) @ w).squeeze(-1) + b  # [T, N, M]
+        ce = -torch.log_softmax(logits, dim=-1).gather(-1, lab64.unsqueeze(-1))
+        loss = scale * ce.sum()
+        loss.backward()
+        return loss
+
+    r, loss_c = fused(), composed()
+    torch.cuda.synchronize()
+    agree = {"loss_rel": abs(float(r.loss) - float(loss_c)) / abs(float(loss_c)),
+             "dhs_normwise": float((r.dhs - hs.grad).abs().max() / hs.grad.abs().max()),
+             "dw_normwise": float((r.dw - w.grad.view(-1)).abs().max() / w.grad.abs().max())}
+    head = {"fused": [], "composed": []}
+    for _ in range(3):
+        fused(), composed()
+    for _ in range(runs):
+        head["fused"].append(round(ev_ms(fused, 10), 4))
+        head["composed"].append(round(ev_ms(composed, 3), 4))
+    del hs.grad, dhs
+    tile = T * N * M * H * 4
+    med = {k: float(np.median(v)) for k, v in head.items()}
+    out = {"config": "S", "M": M, "T": T, "N": N, "Fin": Fin, "H": H, "K": K, "keep_prob": keep,
+           "head_runs_ms": head, "head_median_ms": {k: round(v, 4) for k, v in med.items()},
+           "head_speedup": round(med["composed"] / med["fused"], 2), "head_agreement": agree,
+           # read hs once, write dhs once
+           "head_alg_bytes": 2 * tile, "head_alg_GBps": round(2 * tile / (med["fused"] * 1e-3) / 1e9, 1),
+           "head_share_of_8TBps": round(2 * tile / (med["fused"] * 1e-3) / 8e12, 3)}
+    seams = ("fused", "unfused")
+    models = {s: GConvRNNModel(L, N, T, Fin, num_hidden=H, K=K, keep_prob=keep, seam=s, device=dev)
+              for s in seams}
+    x = 0.5 * torch.randn((N, M, Fin, T), device=dev, generator=g)
+    labels = torch.from_numpy(np.ascontiguousarray(lab_host.T)).to(dev)
+    for m in models.values():
+        for _ in range(3):
+            m.train_step(x, labels)
+    torch.cuda.synchronize()
+    per_run = {s: [] for s in seams}
+    for _ in range(runs):
+        for s in seams:  # interleaved: drift hits both alike
+            per_run[s].append(round(ev_ms(lambda: models[s].train_step(x, labels), 5), 4))
+    lo, hi = min(per_run["unfused"]), max(per_run["unfused"])
+    out.update({"step_runs_ms": per_run,
+                "step_median_ms": {s: round(float(np.median(v)), 4) for s, v in per_run.items()},
+                "unfused_range_ms": [lo, hi]})
+    out["fused_below_unfused_range"] = bool(out["step_median_ms"]["fused"] < lo)
+    out["samples_per_s"] = round(N / (min(out["step_median_ms"].values()) * 1e-3), 1)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("configs", nargs="*", default=["C1", "C2", "D", "E"])
@@ -455,6 +536,8 @@ def main():
             out = resgnn_fourier_config(dev)
         elif name == "EG":
             out = glstm_gconv_config(dev, filter=args.filter)
+        elif name == "S":
+            out = seq_head_config(dev)
         elif name == "R":
             out = resgnn_config(dev)
             cpu = lambda: bench.cpu_baseline_resgnn(graph_e()[1], 2, 100, 2, 32, 20, 4,  # noqa: E731
