@@ -27,6 +27,18 @@ enum Opt { kOptDwDirect = 0, kOptDwW2, kOptDwWaves, kOptSpmmPw, kOptGrp16, kOptG
            kOptSeqXpre, kOptDwX3, kOptGemmX3, kOptMfmaStagger, kOptCount };
 int option(Opt o);
 
+// What the C-ABI translation units (cheb_abi.cpp, fourier_abi.cpp) share: the
+// status an entry returns with the calling thread's cg_last_error text set
+// (fail) or cleared (ok), the workspace rounding, and the launch check.
+int fail(int code, const char* fmt, ...);
+int ok();
+size_t al256(size_t b);
+#define CG_HIP(call)                                                                            \
+  do {                                                                                          \
+    hipError_t e_ = (call);                                                                     \
+    if (e_ != hipSuccess) return cg::fail(CG_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_)); \
+  } while (0)
+
 // Timing-ablation switches (bits 0-7 forward resident kernel, 8-15 backward,
 // 22 skip dW, 23 skip the slab reduction; outputs are WRONG when set).  They
 // exist only in the ablation build (`make debug`, -DCG_DEBUG, a separate .so

@@ -386,9 +386,25 @@ hipError_t launch_gft_prepare(const float* U, int M, void* basis, hipStream_t s)
   return hipGetLastError();
 }
 
+// One launch of k_gft in the mode the call needs: plain (all null), the gate
+// epilogue g, the residual block's EX modes e, or the seam's dropout d (DR 1
+// on the analysis' operand, DR 2 on the synthesis' store).
+struct GftDrop {
+  float keep;
+  unsigned long long seed;
+};
+
+template <bool EX, int DR>
+static void gft_launch(bool x3, dim3 grid, hipStream_t s, const GftArgs& a) {
+  if (x3)
+    hipLaunchKernelGGL((k_gft<true, EX, DR>), grid, dim3(256), 0, s, a);
+  else
+    hipLaunchKernelGGL((k_gft<false, EX, DR>), grid, dim3(256), 0, s, a);
+}
+
 static hipError_t launch_gft_any(const void* basis, int inverse, int N, int M, int C, const float* in,
                                  float* out, bool x3, const GftGate* g, const GftEx* e,
-                                 hipStream_t s) {
+                                 const GftDrop* d, hipStream_t s) {
   GftArgs a{};
   const size_t Mp = size_t(gft_pad(M));
   const char* b = static_cast<const char*>(basis);
@@ -406,56 +422,36 @@ static hipError_t launch_gft_any(const void* basis, int inverse, int N, int M, i
   }
   if (ctiles > 2147483647) return hipErrorInvalidValue;
   const dim3 grid(unsigned(ctiles), unsigned(Mp / kGftTile));
-  if (e) {
+  if (d) {
+    a.keep = d->keep, a.seed = d->seed;
+    if (inverse)
+      gft_launch<false, 2>(x3, grid, s, a);
+    else
+      gft_launch<false, 1>(x3, grid, s, a);
+  } else if (e) {
     a.mask_y = e->mask_y, a.dz = e->dz, a.res = e->residual;
     a.relu = e->relu, a.accum = e->accumulate;
-    if (x3)
-      hipLaunchKernelGGL((k_gft<true, true>), grid, dim3(256), 0, s, a);
-    else
-      hipLaunchKernelGGL((k_gft<false, true>), grid, dim3(256), 0, s, a);
-  } else if (x3) {
-    hipLaunchKernelGGL((k_gft<true, false>), grid, dim3(256), 0, s, a);
+    gft_launch<true, 0>(x3, grid, s, a);
   } else {
-    hipLaunchKernelGGL((k_gft<false, false>), grid, dim3(256), 0, s, a);
-  }
-  return hipGetLastError();
-}
-
-hipError_t launch_gft_drop(const void* basis, int inverse, int N, int M, int C, const float* in,
-                           float* out, bool x3, float keep, unsigned long long seed, hipStream_t s) {
-  GftArgs a{};
-  const size_t Mp = size_t(gft_pad(M));
-  const char* b = static_cast<const char*>(basis);
-  a.A = x3 ? b + size_t(inverse ? 1 : 0) * 3 * Mp * Mp * 2
-           : b + 6 * Mp * Mp * 2 + size_t(inverse ? 1 : 0) * Mp * Mp * 4;
-  a.in = in;
-  a.out = out;
-  a.M = M, a.Mp = int(Mp), a.C = C, a.N = N;
-  a.keep = keep, a.seed = seed;
-  const int64_t ctiles = (int64_t(N) * C + kGftTile - 1) / kGftTile;
-  if (ctiles > 2147483647) return hipErrorInvalidValue;
-  const dim3 grid(unsigned(ctiles), unsigned(Mp / kGftTile));
-  if (inverse) {
-    if (x3)
-      hipLaunchKernelGGL((k_gft<true, false, 2>), grid, dim3(256), 0, s, a);
-    else
-      hipLaunchKernelGGL((k_gft<false, false, 2>), grid, dim3(256), 0, s, a);
-  } else if (x3) {
-    hipLaunchKernelGGL((k_gft<true, false, 1>), grid, dim3(256), 0, s, a);
-  } else {
-    hipLaunchKernelGGL((k_gft<false, false, 1>), grid, dim3(256), 0, s, a);
+    gft_launch<false, 0>(x3, grid, s, a);
   }
   return hipGetLastError();
 }
 
 hipError_t launch_gft(const void* basis, int inverse, int N, int M, int C, const float* in,
                       float* out, bool x3, const GftGate* g, hipStream_t s) {
-  return launch_gft_any(basis, inverse, N, M, C, in, out, x3, g, nullptr, s);
+  return launch_gft_any(basis, inverse, N, M, C, in, out, x3, g, nullptr, nullptr, s);
 }
 
 hipError_t launch_gft_ex(const void* basis, int inverse, int N, int M, int C, const float* in,
                          float* out, bool x3, const GftEx& e, hipStream_t s) {
-  return launch_gft_any(basis, inverse, N, M, C, in, out, x3, nullptr, &e, s);
+  return launch_gft_any(basis, inverse, N, M, C, in, out, x3, nullptr, &e, nullptr, s);
+}
+
+hipError_t launch_gft_drop(const void* basis, int inverse, int N, int M, int C, const float* in,
+                           float* out, bool x3, float keep, unsigned long long seed, hipStream_t s) {
+  const GftDrop d{keep, seed};
+  return launch_gft_any(basis, inverse, N, M, C, in, out, x3, nullptr, nullptr, &d, s);
 }
 
 hipError_t launch_fmix(int form, int64_t R, int M, int Cin, int Cout, const float* W, const float* x,

@@ -43,7 +43,6 @@ and ignored as at lib/graph_conv.py:103, and no Chebyshev plan is built.
 """
 from __future__ import annotations
 
-import ctypes
 import math
 
 import torch
@@ -207,39 +206,26 @@ class _FourierResNet(_ResNet):
     def _f(self, li, x, res, s):
         o = self.o
         _, fi, fo, act = self.layers[li]
-        if li == 0 and self.drop is not None:
-            keep, seed = self.drop
-            st = self._fwd_drop(
-                o.N, o.M, fi, fo, o.gft.data_ptr(), o.gft.numel(), self.W[li].data_ptr(), x.data_ptr(),
-                ctypes.c_float(keep), seed, None, ops.ACTS[act], self.xhat[li].data_ptr(),
-                self.out[li].data_ptr(), o.ws.data_ptr(), o.ws_n, s)
-            _lib.check("cg_fres_forward_drop", st)
-            return self.out[li]
-        st = self._fwd(o.N, o.M, fi, fo, o.gft.data_ptr(), o.gft.numel(), self.W[li].data_ptr(),
-                       x.data_ptr(), res.data_ptr() if res is not None else None, ops.ACTS[act],
-                       self.xhat[li].data_ptr(), self.out[li].data_ptr(), o.ws.data_ptr(), o.ws_n, s)
-        _lib.check("cg_fres_forward", st)
+        # conv_init alone reads through the mask: (keep_prob, seed) go in after x
+        fn, drop = (self._fwd_drop, self.drop) if li == 0 and self.drop is not None else (self._fwd, ())
+        st = fn(o.N, o.M, fi, fo, o.gft.data_ptr(), o.gft.numel(), self.W[li].data_ptr(), x.data_ptr(),
+                *drop, res.data_ptr() if res is not None else None, ops.ACTS[act],
+                self.xhat[li].data_ptr(), self.out[li].data_ptr(), o.ws.data_ptr(), o.ws_n, s)
+        _lib.check(fn.__name__, st)
         return self.out[li]
 
     def _b(self, li, dy, dz, dx, dx_acc, s):
         o = self.o
         _, fi, fo, act = self.layers[li]
-        if li == 0 and self.drop is not None:
-            keep, seed = self.drop
-            st = self._bwd_drop(
-                o.N, o.M, fi, fo, o.gft.data_ptr(), o.gft.numel(), self.W[li].data_ptr(),
+        grads = (dz.data_ptr() if dz is not None else None, dx.data_ptr() if dx is not None else None)
+        if li == 0 and self.drop is not None:  # (keep_prob, seed, dz, dx): dx =, never +=
+            fn, grads = self._bwd_drop, (*self.drop, *grads)
+        else:
+            fn, grads = self._bwd, (*grads, int(dx_acc))
+        st = fn(o.N, o.M, fi, fo, o.gft.data_ptr(), o.gft.numel(), self.W[li].data_ptr(),
                 self.xhat[li].data_ptr(), dy.data_ptr(), self.out[li].data_ptr(), ops.ACTS[act],
-                ctypes.c_float(keep), seed, dz.data_ptr() if dz is not None else None,
-                dx.data_ptr() if dx is not None else None, self.dW[li].data_ptr(), o.ws.data_ptr(),
-                o.ws_n, s)
-            _lib.check("cg_fres_backward_drop", st)
-            return
-        st = self._bwd(o.N, o.M, fi, fo, o.gft.data_ptr(), o.gft.numel(), self.W[li].data_ptr(),
-                       self.xhat[li].data_ptr(), dy.data_ptr(), self.out[li].data_ptr(), ops.ACTS[act],
-                       dz.data_ptr() if dz is not None else None,
-                       dx.data_ptr() if dx is not None else None, int(dx_acc),
-                       self.dW[li].data_ptr(), o.ws.data_ptr(), o.ws_n, s)
-        _lib.check("cg_fres_backward", st)
+                *grads, self.dW[li].data_ptr(), o.ws.data_ptr(), o.ws_n, s)
+        _lib.check(fn.__name__, st)
 
 
 FILTERS = ("chebyshev5", "fourier")

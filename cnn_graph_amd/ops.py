@@ -1228,10 +1228,23 @@ def fres_workspace_bytes(N: int, M: int, Fin: int, Fout: int):
     return fb.value, bb.value
 
 
-def fres_forward(basis, W, x, residual=None, act: str = "none", out_xhat=None, out_y=None):
+def _check_keep(keep_prob):
+    if not 0.0 < float(keep_prob) <= 1.0:
+        raise ValueError(f"keep_prob must be in (0, 1], got {keep_prob}")
+
+
+def fres_forward(basis, W, x, residual=None, act: str = "none", out_xhat=None, out_y=None,
+                 keep_prob: float = 1.0, seed: int = 0, ws=None):
     """y = act(U (W[m] U^T x) + residual) in three launches (cg_fres_forward):
     x [N, M, Fin], W [M, Fout, Fin], basis from gft_prepare.  Returns
-    (xhat [N, M, Fin], y [N, M, Fout])."""
+    (xhat [N, M, Fin], y [N, M, Fout]).
+
+    keep_prob < 1 (cg_fres_forward_drop) is fres_forward of dropout(x, keep_prob,
+    seed) without the dropped tensor: the mask is applied while the analysis
+    stages x -- bit for bit ``dropout`` then ``fres_forward``, and xhat is the
+    dropped x's.  ``seed`` already carries a slice offset (``dropout``'s
+    folding: seed + DROP_WEYL * offset)."""
+    _check_keep(keep_prob)
     for name, t in (("x", x), ("W", W)):
         _check_dev(name, t)
     x, W = x.contiguous(), W.contiguous()
@@ -1249,18 +1262,31 @@ def fres_forward(basis, W, x, residual=None, act: str = "none", out_xhat=None, o
     y = out_y if out_y is not None else torch.empty((N, M, Fout), **f32)
     _check_out("xhat", xhat, (N, M, Fin))
     _check_out("y", y, (N, M, Fout))
-    fb, _ = fres_workspace_bytes(N, M, Fin, Fout)
-    ws = torch.empty(fb, device=x.device, dtype=torch.uint8)
-    _lib.call("cg_fres_forward", N, M, Fin, Fout, _p(basis), basis.numel(), _p(W), _p(x),
-              _p(residual), ACTS[act], _p(xhat), _p(y), _p(ws), fb, _stream(x))
+    if ws is None:
+        ws = torch.empty(fres_workspace_bytes(N, M, Fin, Fout)[0], device=x.device, dtype=torch.uint8)
+    head = (N, M, Fin, Fout, _p(basis), basis.numel(), _p(W), _p(x))
+    tail = (_p(residual), ACTS[act], _p(xhat), _p(y), _p(ws), ws.numel(), _stream(x))
+    if keep_prob == 1.0:
+        _lib.call("cg_fres_forward", *head, *tail)
+    else:
+        _lib.call("cg_fres_forward_drop", *head, float(keep_prob), int(seed) & ((1 << 64) - 1), *tail)
     return xhat, y
 
 
 def fres_backward(basis, W, xhat, dy, y=None, act: str = "none", need_dz: bool = True, dx=None,
-                  dx_accumulate: bool = False, need_dx: bool = True, out_dz=None, out_dW=None):
+                  dx_accumulate: bool = False, need_dx: bool = True, out_dz=None, out_dW=None,
+                  keep_prob: float = 1.0, seed: int = 0, ws=None):
     """Backward through fres_forward (cg_fres_backward): returns (dx, dW, dz)
     with dz = dy * [y > 0] the gradient of the residual input; with
-    dx_accumulate the input gradient is added into the given ``dx``."""
+    dx_accumulate the input gradient is added into the given ``dx``.
+
+    keep_prob < 1 (cg_fres_backward_drop) is the backward of that forward: dx is
+    the gradient of the UNdropped x -- the synthesis stores (acc * mask) /
+    keep_prob, bit for bit ``fres_backward`` then the dropout's backward on dx.
+    It always computes dx and never accumulates."""
+    _check_keep(keep_prob)
+    if keep_prob < 1.0 and (dx_accumulate or not need_dx):
+        raise ValueError("keep_prob < 1 stores dx through the mask: no dx_accumulate, no need_dx=False")
     for name, t in (("W", W), ("xhat", xhat), ("dy", dy)):
         _check_dev(name, t)
     dy, W = dy.contiguous(), W.contiguous()
@@ -1286,84 +1312,31 @@ def fres_backward(basis, W, xhat, dy, y=None, act: str = "none", need_dz: bool =
         _check_out("dz", dz, (N, M, Fout))
     dW = out_dW if out_dW is not None else torch.empty((M, Fout, Fin), **f32)
     _check_out("dW", dW, (M, Fout, Fin))
-    _, bb = fres_workspace_bytes(N, M, Fin, Fout)
-    ws = torch.empty(bb, device=dy.device, dtype=torch.uint8)
-    _lib.call("cg_fres_backward", N, M, Fin, Fout, _p(basis), basis.numel(), _p(W), _p(xhat), _p(dy),
-              _p(y) if act == "relu" else None, ACTS[act], _p(dz), _p(dx), int(dx_accumulate),
-              _p(dW), _p(ws), bb, _stream(dy))
+    if ws is None:
+        ws = torch.empty(fres_workspace_bytes(N, M, Fin, Fout)[1], device=dy.device, dtype=torch.uint8)
+    head = (N, M, Fin, Fout, _p(basis), basis.numel(), _p(W), _p(xhat), _p(dy),
+            _p(y) if act == "relu" else None, ACTS[act])
+    tail = (_p(dW), _p(ws), ws.numel(), _stream(dy))
+    if keep_prob == 1.0:
+        _lib.call("cg_fres_backward", *head, _p(dz), _p(dx), int(dx_accumulate), *tail)
+    else:
+        _lib.call("cg_fres_backward_drop", *head, float(keep_prob), int(seed) & ((1 << 64) - 1), _p(dz),
+                  _p(dx), *tail)
     return dx, dW, dz
-
-
-def _check_keep(keep_prob):
-    if not 0.0 < float(keep_prob) <= 1.0:
-        raise ValueError(f"keep_prob must be in (0, 1], got {keep_prob}")
 
 
 def fres_forward_drop(basis, W, x, keep_prob: float, seed: int, residual=None, act: str = "none",
                       out_xhat=None, out_y=None, ws=None):
-    """fres_forward of dropout(x, keep_prob, seed) without the dropped tensor
-    (cg_fres_forward_drop): the mask is applied while the analysis stages x --
-    bit for bit ``dropout`` then ``fres_forward``.  ``seed`` already carries a
-    slice offset (``dropout``'s folding: seed + DROP_WEYL * offset).  Returns
-    (xhat of the dropped x [N, M, Fin], y [N, M, Fout])."""
-    _check_keep(keep_prob)
-    for name, t in (("x", x), ("W", W)):
-        _check_dev(name, t)
-    x, W = x.contiguous(), W.contiguous()
-    N, M, Fin = (int(s) for s in x.shape)
-    if W.dim() != 3 or tuple(W.shape[::2]) != (M, Fin):
-        raise ValueError(f"W must be [M, Fout, Fin] = [{M}, *, {Fin}], got {tuple(W.shape)}")
-    Fout = int(W.shape[1])
-    f32 = dict(device=x.device, dtype=torch.float32)
-    if residual is not None:
-        _check_dev("residual", residual)
-        residual = residual.contiguous()
-        if residual.numel() != N * M * Fout:
-            raise ValueError(f"residual must be [N, M, Fout] = [{N}, {M}, {Fout}]")
-    xhat = out_xhat if out_xhat is not None else torch.empty((N, M, Fin), **f32)
-    y = out_y if out_y is not None else torch.empty((N, M, Fout), **f32)
-    _check_out("xhat", xhat, (N, M, Fin))
-    _check_out("y", y, (N, M, Fout))
-    if ws is None:
-        ws = torch.empty(fres_workspace_bytes(N, M, Fin, Fout)[0], device=x.device, dtype=torch.uint8)
-    _lib.call("cg_fres_forward_drop", N, M, Fin, Fout, _p(basis), basis.numel(), _p(W), _p(x),
-              float(keep_prob), int(seed) & ((1 << 64) - 1), _p(residual), ACTS[act], _p(xhat), _p(y),
-              _p(ws), ws.numel(), _stream(x))
-    return xhat, y
+    """fres_forward with the seam's arguments in front (cg_fres_forward_drop)."""
+    return fres_forward(basis, W, x, residual, act, out_xhat, out_y, keep_prob, seed, ws)
 
 
 def fres_backward_drop(basis, W, xhat, dy, keep_prob: float, seed: int, y=None, act: str = "none",
                        need_dz: bool = True, out_dx=None, out_dz=None, out_dW=None, ws=None):
-    """Backward through fres_forward_drop (cg_fres_backward_drop): returns
-    (dx, dW, dz) with dx the gradient of the UNdropped x -- the synthesis stores
-    (acc * mask) / keep_prob, bit for bit ``fres_backward`` then the dropout's
-    backward on dx.  dx is always computed."""
-    _check_keep(keep_prob)
-    for name, t in (("W", W), ("xhat", xhat), ("dy", dy)):
-        _check_dev(name, t)
-    dy, W = dy.contiguous(), W.contiguous()
-    N, M, Fout = (int(s) for s in dy.shape)
-    Fin = int(W.shape[2])
-    f32 = dict(device=dy.device, dtype=torch.float32)
-    if act == "relu":
-        if y is None:
-            raise ValueError("act relu needs the forward's output y")
-        _check_out("y", y, (N, M, Fout))
-    _check_out("xhat", xhat, (N, M, Fin))
-    dx = out_dx if out_dx is not None else torch.empty((N, M, Fin), **f32)
-    _check_out("dx", dx, (N, M, Fin))
-    dz = None
-    if need_dz:
-        dz = out_dz if out_dz is not None else torch.empty((N, M, Fout), **f32)
-        _check_out("dz", dz, (N, M, Fout))
-    dW = out_dW if out_dW is not None else torch.empty((M, Fout, Fin), **f32)
-    _check_out("dW", dW, (M, Fout, Fin))
-    if ws is None:
-        ws = torch.empty(fres_workspace_bytes(N, M, Fin, Fout)[1], device=dy.device, dtype=torch.uint8)
-    _lib.call("cg_fres_backward_drop", N, M, Fin, Fout, _p(basis), basis.numel(), _p(W), _p(xhat),
-              _p(dy), _p(y) if act == "relu" else None, ACTS[act], float(keep_prob),
-              int(seed) & ((1 << 64) - 1), _p(dz), _p(dx), _p(dW), _p(ws), ws.numel(), _stream(dy))
-    return dx, dW, dz
+    """fres_backward with the seam's arguments in front (cg_fres_backward_drop);
+    dx is always computed."""
+    return fres_backward(basis, W, xhat, dy, y, act, need_dz, dx=out_dx, out_dz=out_dz, out_dW=out_dW,
+                         keep_prob=keep_prob, seed=seed, ws=ws)
 
 
 class _FourierAct(torch.autograd.Function):
