@@ -1,6 +1,7 @@
 // C ABI of libcheb_mi355.so (see include/cheb_mi355.h): plan management,
-// argument validation, workspace layout and kernel-path dispatch.  (The Fourier
-// filter family's entries are fourier_abi.cpp.)
+// options, argument validation, workspace layout and kernel-path dispatch of the
+// cg_plan_* and cg_cheb_* entries.  (The gconv-LSTM entries are lstm_abi.cpp, the
+// training ops train_abi.cpp, the Fourier filter family fourier_abi.cpp.)
 #include "../../include/cheb_mi355.h"
 #include "../../include/cheb_mi355_testing.h"
 
@@ -16,6 +17,8 @@
 #include <string>
 #include <vector>
 
+#include "abi_checks.h"
+#include "abi_plan.h"
 #include "cg_internal.h"
 
 #ifdef CG_DEBUG
@@ -25,55 +28,6 @@ int g_debug_params[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
 unsigned long long* g_debug_ts = nullptr;
 }
 #endif
-
-struct cg_plan {
-  int device = 0;
-  int M = 0;
-  int64_t nnz = 0, nnzT = 0;
-  int max_row_nnz = 0, max_row_nnzT = 0;
-  int path = CG_PATH_AUTO;
-  int variant = CG_VARIANT_AUTO;
-  int* rowptr = nullptr;
-  int* col = nullptr;
-  float* val = nullptr;
-  int* trowptr = nullptr;
-  int* tcol = nullptr;
-  float* tval = nullptr;
-  // degree-sorted row orders of L~ / L~^T (longest rows first), used by the
-  // streaming steps on skewed (power-law) graphs so a wave's rows have similar
-  // lengths; null when the row lengths are near-uniform
-  int* rperm = nullptr;
-  int* trperm = nullptr;
-  // rows of L~ / L~^T by decreasing length, always present: the LDS-resident
-  // kernels deal rows to lanes in this order so a wave's rows have (nearly)
-  // equal lengths and its unrolled gather loop has no idle entries
-  int* lorder = nullptr;
-  int* tlorder = nullptr;
-  // thread-slot images of L~ and L~^T for the resident kernels (M <= 2048)
-  struct Slots {
-    int* buf = nullptr;  // one allocation: row | len | beg | col | val | wlen
-    cg::SlotLayout view{};
-  } slots, tslots;
-  // images of L~ and L~^T for the fast resident kernels (cheb_fast.hip)
-  struct Fast {
-    void* buf = nullptr;
-    cg::FastImage view{};
-    bool ok = false;  // max row length <= cg::kFastWidth and M <= 1024
-    long gather_cycles = 0, gather_ideal = 0;  // modelled LDS cycles per step
-  } fast, tfast;
-  // the gconv-LSTM sequence launches' sticky fault word: host-mapped pinned
-  // memory the kernel writes (system scope) when a pair hand-off times out,
-  // read by cg_lstm_seq_fault without a device copy once seq_event (recorded
-  // behind every sequence launch) has completed
-  int* seq_fault = nullptr;      // host pointer
-  int* seq_fault_dev = nullptr;  // its device alias
-  hipEvent_t seq_event = nullptr;
-  bool seq_launched = false;
-  // test hook (cg_plan_set_seq_fault_test): >= 0 makes workgroup 0 of pair 0
-  // of this plan's sequence launches stop publishing its step counter from
-  // that step on; -1 (default) off
-  int seq_fault_test = -1;
-};
 
 namespace {
 thread_local std::string g_err;  // the calling thread's last-error text
@@ -98,7 +52,10 @@ int cg::ok() {
 size_t cg::al256(size_t b) { return (b + 255) & ~size_t(255); }
 
 using cg::al256;
+using cg::check_device;
+using cg::dw_slab_bytes;
 using cg::fail;
+using cg::need_ws;
 using cg::ok;
 
 namespace {
@@ -298,15 +255,6 @@ void free_plan(cg_plan* p) {
   delete p;
 }
 
-int check_device(const cg_plan* p) {
-  int d = -1;
-  CG_HIP(hipGetDevice(&d));
-  if (d != p->device)
-    return fail(CG_ERR_ARG, "current HIP device %d differs from the plan's device %d", d,
-                p->device);
-  return CG_OK;
-}
-
 int check_shape(const cg_plan* p, int32_t N, int32_t Fin, int32_t K, int32_t Fout) {
   if (!p) return fail(CG_ERR_ARG, "null plan");
   if (N < 1 || Fin < 1 || K < 1 || Fout < 1)
@@ -386,15 +334,6 @@ int check_layout(const cg_plan* p, int32_t Fin, int32_t K, int32_t Fout, int lay
                 "fused-dW fast backward (M=%d Fin=%d K=%d Fout=%d)",
                 p->M, Fin, K, Fout);
   return CG_OK;
-}
-
-// dW partial slabs: dw_chunks(R) of them from k_dw_slabs, or one per sample
-// from the fused backward.
-// M > 0: the wide path's fused dy pass writes the slabs (one per block)
-size_t dw_slab_bytes(int64_t R, int32_t N, int FinK, int Fout, int32_t M = 0) {
-  size_t n = std::max<size_t>(size_t(cg::dw_chunks(R)), size_t(N));
-  if (M > 0) n = std::max<size_t>(n, size_t(cg::wide_dypass_blocks(N, M)));
-  return al256(n * size_t(FinK) * size_t(Fout) * 4);
 }
 
 // What a Chebyshev convolution launches and where its buffers lie, decided once
@@ -889,8 +828,7 @@ int forward_impl(cg_plan* plan, int32_t N, int32_t Fin, int32_t K, int32_t Fout,
   }
   // streaming path
   if (!basis) return fail(CG_ERR_ARG, "streaming path needs a basis buffer (the GEMM reads it)");
-  if (r.fwd_bytes && (!workspace || ws_bytes < r.fwd_bytes))
-    return fail(CG_ERR_ARG, "forward workspace too small: %zu < %zu", ws_bytes, r.fwd_bytes);
+  if (r.fwd_bytes && (rc = need_ws("forward", workspace, ws_bytes, r.fwd_bytes))) return rc;
   float* slots = static_cast<float*>(workspace);
   const size_t slot = size_t(M) * size_t(N) * size_t(Fin);
   switch (r.fwd) {
@@ -994,8 +932,7 @@ int backward_impl(cg_plan* plan, int32_t N, int32_t Fin, int32_t K, int32_t Fout
   if ((rc = check_device(plan))) return rc;
   ChebRoute r;
   if ((rc = cheb_route(plan, N, Fin, K, Fout, layout, true, &r))) return rc;
-  if (!workspace || ws_bytes < r.bwd_bytes)
-    return fail(CG_ERR_ARG, "backward workspace too small: %zu < %zu", ws_bytes, r.bwd_bytes);
+  if ((rc = need_ws("backward", workspace, ws_bytes, r.bwd_bytes))) return rc;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int M = plan->M;
   const int FinK = Fin * K;
@@ -1144,19 +1081,14 @@ int backward_adam_impl(cg_plan* plan, int32_t N, int32_t Fin, int32_t K, int32_t
     return fail(CG_ERR_ARG, "cheb_backward_adam: dW, W, m, v required and step >= 1");
   // the reduction stores grad[i] and then updates param/m/v[i] in place:
   // any two of them sharing memory would corrupt the update
-  const void* bufs[4] = {dW, W, m, v};
-  for (int i = 0; i < 4; ++i)
-    for (int j = i + 1; j < 4; ++j)
-      if (bufs[i] == bufs[j])
-        return fail(CG_ERR_ARG, "cheb_backward_adam: dW, W, m and v must be distinct buffers");
+  if (int rc = cg::all_distinct("cheb_backward_adam: dW, W, m and v", {dW, W, m, v})) return rc;
   if (cg::debug_flags() & ((1 << 22) | (1 << 23)))
     return fail(CG_ERR_UNSUPPORTED, "cheb_backward_adam: dW ablation bits would corrupt W");
   cg::AdamStep a{};
   a.param = W;
   a.m = m;
   a.v = v;
-  a.lr_t = float(double(lr) * std::sqrt(1.0 - std::pow(double(beta2), step)) /
-                 (1.0 - std::pow(double(beta1), step)));
+  a.lr_t = cg::adam_lr_t(lr, beta1, beta2, step);
   a.beta1 = beta1;
   a.beta2 = beta2;
   a.eps = eps;
@@ -1237,19 +1169,11 @@ int cg_cheb_forward_adam(cg_plan* plan, int32_t N, int32_t Fin, int32_t K, int32
                             "and step >= 1");
   // every workgroup reads W, m, v while workgroup 0 writes W', m', v': the
   // outputs must not alias any input
-  const void* outs[3] = {W_out, m_out, v_out};
-  const void* ins[4] = {W, grad, m, v};
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 4; ++j)
-      if (outs[i] == ins[j])
-        return fail(CG_ERR_ARG, "cheb_forward_adam: W_out, m_out, v_out must not alias the inputs");
-    for (int j = i + 1; j < 3; ++j)
-      if (outs[i] == outs[j])
-        return fail(CG_ERR_ARG, "cheb_forward_adam: W_out, m_out, v_out must be distinct");
-  }
-  FwdAdam fa{grad, m, v, W_out, m_out, v_out,
-             float(double(lr) * std::sqrt(1.0 - std::pow(double(beta2), step)) /
-                   (1.0 - std::pow(double(beta1), step))),
+  const char* outs = "cheb_forward_adam: W_out, m_out, v_out";
+  int rc = cg::no_alias(outs, {W_out, m_out, v_out}, {W, grad, m, v});
+  if (!rc) rc = cg::all_distinct(outs, {W_out, m_out, v_out});
+  if (rc) return rc;
+  FwdAdam fa{grad, m, v, W_out, m_out, v_out, cg::adam_lr_t(lr, beta1, beta2, step),
              beta1, beta2, eps, grad_scale};
   return forward_impl(plan, N, Fin, K, Fout, x, W, nullptr, CG_ACT_NONE, basis, y, workspace,
                       ws_bytes, stream, layout, &fa);
@@ -1272,479 +1196,6 @@ int cg_cheb_backward_adam_layout(cg_plan* plan, int32_t N, int32_t Fin, int32_t 
                             beta2, eps, step, grad_scale, workspace, ws_bytes, stream);
 }
 
-int cg_mse_loss_workspace_bytes(int64_t n, size_t* bytes) {
-  if (!bytes || n < 1) return fail(CG_ERR_ARG, "mse_loss: bad arguments");
-  *bytes = al256(size_t(cg::mse_chunks(n)) * 4);
-  return ok();
-}
-
-int cg_mse_loss(const float* pred, const float* labels, int64_t n, float* loss, float* dpred,
-                void* workspace, size_t ws_bytes, void* stream) {
-  if (!pred || !labels || !loss || n < 1) return fail(CG_ERR_ARG, "mse_loss: bad arguments");
-  const size_t need = al256(size_t(cg::mse_chunks(n)) * 4);
-  if (!workspace || ws_bytes < need)
-    return fail(CG_ERR_ARG, "mse_loss workspace too small: %zu < %zu", ws_bytes, need);
-  CG_HIP(cg::launch_mse(pred, labels, n, static_cast<float*>(workspace), loss, dpred,
-                        reinterpret_cast<hipStream_t>(stream)));
-  return ok();
-}
-
-int cg_mse_loss_ema(const float* pred, const float* labels, int64_t n, float* loss, float* dpred,
-                    float* ema, float decay, void* workspace, size_t ws_bytes, void* stream) {
-  if (!pred || !labels || !loss || !ema || n < 1 || !(decay >= 0.f && decay <= 1.f))
-    return fail(CG_ERR_ARG, "mse_loss_ema: bad arguments");
-  const size_t need = al256(size_t(cg::mse_chunks(n)) * 4);
-  if (!workspace || ws_bytes < need)
-    return fail(CG_ERR_ARG, "mse_loss_ema workspace too small: %zu < %zu", ws_bytes, need);
-  CG_HIP(cg::launch_mse(pred, labels, n, static_cast<float*>(workspace), loss, dpred,
-                        reinterpret_cast<hipStream_t>(stream), ema, decay));
-  return ok();
-}
-
-int cg_dropout_forward(const float* x, int64_t n, float keep_prob, uint64_t seed, float* y,
-                       void* stream) {
-  if (!x || !y || n < 1 || !(keep_prob > 0.f && keep_prob <= 1.f))
-    return fail(CG_ERR_ARG, "dropout_forward: bad arguments (keep_prob=%g)", keep_prob);
-  CG_HIP(cg::launch_dropout(x, y, n, keep_prob, seed, 0, reinterpret_cast<hipStream_t>(stream)));
-  return ok();
-}
-
-int cg_dropout_backward(const float* dy, int64_t n, float keep_prob, uint64_t seed, float* dx,
-                        void* stream) {
-  if (!dy || !dx || n < 1 || !(keep_prob > 0.f && keep_prob <= 1.f))
-    return fail(CG_ERR_ARG, "dropout_backward: bad arguments (keep_prob=%g)", keep_prob);
-  CG_HIP(cg::launch_dropout(dy, dx, n, keep_prob, seed, 1, reinterpret_cast<hipStream_t>(stream)));
-  return ok();
-}
-
-int cg_clip_by_norm(float* t, int64_t n, float clip_norm, int32_t* nonfinite, void* stream) {
-  if (!t || n < 1 || !(clip_norm > 0.f))
-    return fail(CG_ERR_ARG, "clip_by_norm: bad arguments (n=%lld, clip_norm=%g)", (long long)n,
-                clip_norm);
-  CG_HIP(cg::launch_clip_norm(t, n, clip_norm, nonfinite, reinterpret_cast<hipStream_t>(stream)));
-  return ok();
-}
-
-int cg_seq_xent_workspace_bytes(int32_t T, int32_t N, int32_t M, int32_t H, size_t* out) {
-  if (!out || T < 1 || N < 1 || M < 1 || H < 1 || int64_t(T) * N > INT32_MAX)
-    return fail(CG_ERR_ARG, "seq_xent_workspace_bytes: bad arguments");
-  if (H > 256) return fail(CG_ERR_UNSUPPORTED, "seq_xent: H = %d, the head supports H <= 256", H);
-  *out = al256(cg::seq_xent_ws_bytes(int64_t(T) * N, M, H));
-  return ok();
-}
-
-int cg_seq_xent_head(const float* hs, const float* w, const float* b, const int32_t* labels,
-                     int32_t T, int32_t N, int32_t M, int32_t H, float keep, uint64_t seed,
-                     float loss_scale, float* logits, float* ce, float* loss, float* dhs, float* dw,
-                     float* db, void* ws, size_t ws_bytes, void* stream) {
-  if (!hs || !w || !b || !labels || !loss || (dhs && (!dw || !db)))
-    return fail(CG_ERR_ARG, "seq_xent_head: null pointer");
-  if (T < 1 || N < 1 || M < 1 || H < 1 || int64_t(T) * N > INT32_MAX)
-    return fail(CG_ERR_ARG, "seq_xent_head: bad sizes (T=%d N=%d M=%d H=%d)", T, N, M, H);
-  if (!(keep > 0.f && keep <= 1.f))
-    return fail(CG_ERR_ARG, "seq_xent_head: keep = %g outside (0, 1]", keep);
-  if (H > 256) return fail(CG_ERR_UNSUPPORTED, "seq_xent: H = %d, the head supports H <= 256", H);
-  const size_t need = al256(cg::seq_xent_ws_bytes(int64_t(T) * N, M, H));
-  if (!ws || ws_bytes < need)
-    return fail(CG_ERR_ARG, "seq_xent_head workspace too small: %zu < %zu", ws_bytes, need);
-  CG_HIP(cg::launch_seq_xent(hs, w, b, labels, T, N, M, H, keep, seed, loss_scale, logits, ce, loss,
-                             dhs, dw, db, static_cast<float*>(ws),
-                             reinterpret_cast<hipStream_t>(stream)));
-  return ok();
-}
-
-int cg_slice_channels(const float* x, int64_t rows, int32_t C, int32_t c0, int32_t c1, float* out,
-                      void* stream) {
-  if (!x || !out || rows < 1 || C < 1 || c0 < 0 || c1 <= c0 || c1 > C)
-    return fail(CG_ERR_ARG, "slice_channels: bad arguments (C=%d, [%d, %d))", C, c0, c1);
-  CG_HIP(cg::launch_slice_channels(x, rows, C, c0, c1, out, reinterpret_cast<hipStream_t>(stream)));
-  return ok();
-}
-
-int cg_stack_merge_forward(int32_t N, int32_t M, int32_t F, const float* out_i, const float* w_i,
-                           int32_t accumulate, float* y, void* stream) {
-  if (N < 1 || M < 1 || F < 1 || !out_i || !w_i || !y)
-    return fail(CG_ERR_ARG, "stack_merge_forward: bad arguments");
-  if (out_i == y) return fail(CG_ERR_ARG, "stack_merge_forward: y must not alias out_i");
-  CG_HIP(cg::launch_stack_merge_fwd(out_i, w_i, N, int64_t(M) * F, accumulate, y,
-                                    reinterpret_cast<hipStream_t>(stream)));
-  return ok();
-}
-
-int cg_stack_merge_backward(int32_t N, int32_t M, int32_t F, const float* dy, const float* out_i,
-                            const float* w_i, float* dout_i, float* dw_i, void* stream) {
-  if (N < 1 || M < 1 || F < 1 || !dy || !out_i || !w_i || (!dout_i && !dw_i))
-    return fail(CG_ERR_ARG, "stack_merge_backward: bad arguments");
-  if (dout_i && (dout_i == out_i || dout_i == dy))
-    return fail(CG_ERR_ARG, "stack_merge_backward: dout_i must not alias dy / out_i");
-  CG_HIP(cg::launch_stack_merge_bwd(dy, out_i, w_i, N, int64_t(M) * F, dout_i, dw_i,
-                                    reinterpret_cast<hipStream_t>(stream)));
-  return ok();
-}
-
-int cg_weight_grad_workspace_bytes(int64_t R, int32_t FinK, int32_t Fout, size_t* bytes) {
-  if (!bytes || R < 1 || FinK < 1 || Fout < 1) return fail(CG_ERR_ARG, "weight_grad: bad arguments");
-  *bytes = dw_slab_bytes(R, 0, FinK, Fout);
-  return ok();
-}
-
-int cg_weight_grad(int64_t R, int32_t FinK, int32_t Fout, const float* basis, const float* dy,
-                   float* dW, int32_t accumulate, void* workspace, size_t ws_bytes, void* stream) {
-  if (!basis || !dy || !dW || R < 1 || FinK < 1 || Fout < 1)
-    return fail(CG_ERR_ARG, "weight_grad: bad arguments");
-  const size_t need = dw_slab_bytes(R, 0, FinK, Fout);
-  if (!workspace || ws_bytes < need)
-    return fail(CG_ERR_ARG, "weight_grad workspace too small: %zu < %zu", ws_bytes, need);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  float* slabs = static_cast<float*>(workspace);
-  CG_HIP(cg::launch_dw_slabs(basis, dy, R, FinK, Fout, slabs, s));
-  CG_HIP(cg::launch_reduce_slabs_acc(slabs, cg::dw_chunks(R), int64_t(FinK) * Fout, dW,
-                                     accumulate != 0, s));
-  return ok();
-}
-
-int cg_weight_grad_planes(int64_t R, int32_t Fin, int32_t K, int32_t Fout, const float* planes,
-                          int64_t plane_stride, const float* dy, float* dW, int32_t accumulate,
-                          void* workspace, size_t ws_bytes, void* stream) {
-  if (!planes || !dy || !dW || R < 1 || Fin < 1 || K < 1 || Fout < 1 || plane_stride < R * Fin)
-    return fail(CG_ERR_ARG, "weight_grad_planes: bad arguments");
-  const int FinK = Fin * K;
-  const size_t need = dw_slab_bytes(R, 0, FinK, Fout);
-  if (!workspace || ws_bytes < need)
-    return fail(CG_ERR_ARG, "weight_grad_planes workspace too small: %zu < %zu", ws_bytes, need);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  float* slabs = static_cast<float*>(workspace);
-  CG_HIP(cg::launch_dw_slabs(planes, dy, R, FinK, Fout, slabs, s, Fin, plane_stride, K));
-  CG_HIP(cg::launch_reduce_slabs_acc(slabs, cg::dw_chunks(R), int64_t(FinK) * Fout, dW,
-                                     accumulate != 0, s));
-  return ok();
-}
-
-static size_t lstm_wgrad_rows(int32_t H, int32_t Fin, int32_t K) {
-  return size_t(H + Fin) * size_t(K) + 1;
-}
-
-int cg_lstm_weight_grads_workspace_bytes(int64_t R, int32_t H, int32_t Fin, int32_t K,
-                                         size_t* bytes) {
-  if (!bytes || R < 1 || H < 1 || Fin < 1 || K < 1)
-    return fail(CG_ERR_ARG, "lstm_weight_grads: bad arguments");
-  const size_t rows = lstm_wgrad_rows(H, Fin, K);
-  *bytes = dw_slab_bytes(R, 0, int(rows), 4 * H) + al256(rows * size_t(4 * H) * 4);
-  return ok();
-}
-
-int cg_lstm_weight_grads(int64_t R, int32_t H, int32_t Fin, int32_t K, const float* h_planes,
-                         int64_t h_plane_stride, const float* x_planes, int64_t x_plane_stride,
-                         const float* dpre, float* dWh, float* dWx, float* db, void* workspace,
-                         size_t ws_bytes, void* stream) {
-  if (!h_planes || !x_planes || !dpre || !dWh || !dWx || !db || R < 1 || H < 1 || Fin < 1 ||
-      K < 1 || h_plane_stride < R * H || x_plane_stride < R * Fin)
-    return fail(CG_ERR_ARG, "lstm_weight_grads: bad arguments");
-  if (4 * H > 256 || Fin * K + 1 > 64)
-    return fail(CG_ERR_UNSUPPORTED, "lstm_weight_grads: needs 4H <= 256, Fin*K < 64 (H=%d Fin=%d K=%d)",
-                H, Fin, K);
-  size_t need = 0;
-  int rc = cg_lstm_weight_grads_workspace_bytes(R, H, Fin, K, &need);
-  if (rc) return rc;
-  if (!workspace || ws_bytes < need)
-    return fail(CG_ERR_ARG, "lstm_weight_grads workspace too small: %zu < %zu", ws_bytes, need);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int rows = int(lstm_wgrad_rows(H, Fin, K)), C = 4 * H;
-  const size_t slab_bytes = dw_slab_bytes(R, 0, rows, C);
-  float* slabs = static_cast<float*>(workspace);
-  float* comb = reinterpret_cast<float*>(static_cast<char*>(workspace) + slab_bytes);
-  CG_HIP(cg::launch_dw_slabs(h_planes, dpre, R, H * K, C, slabs, s, H, h_plane_stride, K, x_planes,
-                             Fin, x_plane_stride));
-  (void)comb;
-  // the fixed-order slab sums straight into dWh | dWx | db (one launch, no copies)
-  CG_HIP(cg::launch_reduce_slabs3(slabs, cg::dw_chunks(R), int64_t(rows) * C, dWh,
-                                  int64_t(H) * K * C, dWx, int64_t(H + Fin) * K * C, db, s));
-  return ok();
-}
-
-int cg_bias_grad_workspace_bytes(int64_t R, int32_t C, size_t* bytes) {
-  if (!bytes || R < 1 || C < 1) return fail(CG_ERR_ARG, "bias_grad: bad arguments");
-  *bytes = al256(size_t(cg::colsum_chunks(R)) * size_t(C) * 4);
-  return ok();
-}
-
-int cg_bias_grad(int64_t R, int32_t C, const float* dy, float* db, int32_t accumulate,
-                 void* workspace, size_t ws_bytes, void* stream) {
-  if (!dy || !db || R < 1 || C < 1) return fail(CG_ERR_ARG, "bias_grad: bad arguments");
-  const size_t need = al256(size_t(cg::colsum_chunks(R)) * size_t(C) * 4);
-  if (!workspace || ws_bytes < need)
-    return fail(CG_ERR_ARG, "bias_grad workspace too small: %zu < %zu", ws_bytes, need);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  float* slabs = static_cast<float*>(workspace);
-  CG_HIP(cg::launch_colsum_slabs(dy, R, C, slabs, s));
-  CG_HIP(cg::launch_reduce_slabs_acc(slabs, cg::colsum_chunks(R), C, db, accumulate != 0, s));
-  return ok();
-}
-
-// ---- bias + activation (b1relu / b1tanh / b2relu) and fc GEMM -----------------
-int cg_bias_act_forward(int64_t n, int32_t bias_len, const float* x, const float* bias,
-                        int32_t act, float* y, void* stream) {
-  if (!x || !y || n < 1) return fail(CG_ERR_ARG, "bias_act_forward: bad arguments");
-  if (act < CG_ACT_NONE || act > CG_ACT_TANH) return fail(CG_ERR_ARG, "unknown activation %d", act);
-  if (bias && (bias_len < 1 || n % bias_len))
-    return fail(CG_ERR_ARG, "bias_act_forward: n=%lld is not a multiple of bias_len=%d",
-                (long long)n, bias_len);
-  CG_HIP(cg::launch_bias_act_fwd(x, bias, bias ? bias_len : 1, act, n, y,
-                                 reinterpret_cast<hipStream_t>(stream)));
-  return ok();
-}
-
-int cg_bias_act_workspace_bytes(int64_t n, int32_t bias_len, size_t* bytes) {
-  if (!bytes || n < 1 || bias_len < 1 || n % bias_len)
-    return fail(CG_ERR_ARG, "bias_act_workspace_bytes: bad arguments");
-  *bytes = al256(size_t(cg::colsum_chunks(n / bias_len)) * size_t(bias_len) * 4);
-  return ok();
-}
-
-int cg_bias_act_backward(int64_t n, int32_t bias_len, const float* dy, const float* y, int32_t act,
-                         float* dz, float* db, int32_t accumulate, void* workspace,
-                         size_t ws_bytes, void* stream) {
-  if (!dy || !dz || n < 1) return fail(CG_ERR_ARG, "bias_act_backward: bad arguments");
-  if (act < CG_ACT_NONE || act > CG_ACT_TANH) return fail(CG_ERR_ARG, "unknown activation %d", act);
-  if (act != CG_ACT_NONE && !y) return fail(CG_ERR_ARG, "bias_act_backward: activation needs y");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  CG_HIP(cg::launch_bias_act_bwd(dy, y, act, n, dz, s));
-  if (!db) return ok();
-  if (bias_len < 1 || n % bias_len)
-    return fail(CG_ERR_ARG, "bias_act_backward: n=%lld is not a multiple of bias_len=%d",
-                (long long)n, bias_len);
-  const int64_t R = n / bias_len;
-  const size_t need = al256(size_t(cg::colsum_chunks(R)) * size_t(bias_len) * 4);
-  if (!workspace || ws_bytes < need)
-    return fail(CG_ERR_ARG, "bias_act workspace too small: %zu < %zu", ws_bytes, need);
-  float* slabs = static_cast<float*>(workspace);
-  CG_HIP(cg::launch_colsum_slabs(dz, R, bias_len, slabs, s));
-  CG_HIP(cg::launch_reduce_slabs_acc(slabs, cg::colsum_chunks(R), bias_len, db, accumulate != 0, s));
-  return ok();
-}
-
-int cg_gemm_f32(int32_t trans_a, int32_t trans_b, int32_t M, int32_t N, int32_t K, const float* A,
-                int32_t lda, const float* B, int32_t ldb, float* C, int32_t ldc, void* stream) {
-  if (!A || !B || !C || M < 1 || N < 1 || K < 1) return fail(CG_ERR_ARG, "gemm_f32: bad arguments");
-  if (lda < (trans_a ? M : K) || ldb < (trans_b ? K : N) || ldc < N)
-    return fail(CG_ERR_ARG, "gemm_f32: leading dimension too small (lda=%d ldb=%d ldc=%d)", lda, ldb,
-                ldc);
-  if ((M + 63) / 64 > 2147483647 / 2 || (N + 63) / 64 > 65535)
-    return fail(CG_ERR_ARG, "gemm_f32: N=%d too large for the grid", N);
-  CG_HIP(cg::launch_gemm_f32(trans_a != 0, trans_b != 0, M, N, K, A, lda, B, ldb, C, ldc, 1,
-                             reinterpret_cast<hipStream_t>(stream)));
-  return ok();
-}
-
-static int check_lstm(int64_t R, int32_t H, int32_t gates) {
-  if (R < 1 || H < 1) return fail(CG_ERR_ARG, "lstm: bad shape R=%lld H=%d", (long long)R, H);
-  if (R * int64_t(H) * 4 >= (int64_t(1) << 31))
-    return fail(CG_ERR_ARG, "lstm: R*4H = %lld exceeds 2^31", (long long)(R * H * 4));
-  if (gates != CG_LSTM_GATES_REFERENCE && gates != CG_LSTM_GATES_STANDARD)
-    return fail(CG_ERR_ARG, "lstm: unknown gate set %d", gates);
-  return CG_OK;
-}
-
-int cg_lstm_cell_forward(int64_t R, int32_t H, int32_t gates, const float* gx, const float* gh,
-                         const float* bias, const float* c, float* c_out, float* h_out, float* act,
-                         void* stream) {
-  int rc = check_lstm(R, H, gates);
-  if (rc) return rc;
-  if (!gx || !c_out || !h_out) return fail(CG_ERR_ARG, "lstm_cell_forward: null gx/c_out/h_out");
-  CG_HIP(cg::launch_lstm_fwd(gates, R, H, gx, gh, bias, c, c_out, h_out, act,
-                             reinterpret_cast<hipStream_t>(stream)));
-  return ok();
-}
-
-int cg_lstm_cell_backward(int64_t R, int32_t H, int32_t gates, const float* dh,
-                          const float* dh_rec, const float* dc,
-                          const float* act, const float* c, const float* c_out, float* dpre,
-                          float* dc_prev, void* stream) {
-  int rc = check_lstm(R, H, gates);
-  if (rc) return rc;
-  if (!act || !c_out || !dpre) return fail(CG_ERR_ARG, "lstm_cell_backward: null act/c_out/dpre");
-  CG_HIP(cg::launch_lstm_bwd(gates, R, H, dh, dh_rec, dc, act, c, c_out, dpre, dc_prev,
-                             reinterpret_cast<hipStream_t>(stream)));
-  return ok();
-}
-
-int cg_lstm_hconv_supported(const cg_plan* plan, int32_t H, int32_t K, int32_t* supported) {
-  if (!plan || !supported) return fail(CG_ERR_ARG, "lstm_hconv_supported: null argument");
-  *supported = cg::lstm_hstep_ok(plan->M, H, K) ? 1 : 0;
-  return ok();
-}
-
-int cg_lstm_hconv_step(cg_plan* plan, int32_t N, int32_t H, int32_t K, int32_t gates,
-                       const float* h_prev, const float* c_prev, const float* gx, const float* Wh,
-                       const float* bias, float* c_out, float* h_out, float* act, float* planes,
-                       int64_t plane_stride, void* stream) {
-  int rc = check_lstm(int64_t(N) * (plan ? plan->M : 1), H, gates);
-  if (rc) return rc;
-  if (!plan || N < 1 || K < 1) return fail(CG_ERR_ARG, "lstm_hconv_step: bad plan / N / K");
-  if (!h_prev || !gx || !Wh || !c_out || !h_out)
-    return fail(CG_ERR_ARG, "lstm_hconv_step: null h_prev / gx / Wh / c_out / h_out");
-  if (!cg::lstm_hstep_ok(plan->M, H, K))
-    return fail(CG_ERR_UNSUPPORTED, "lstm_hconv_step: needs H = 32, M <= 1024 and the LDS for K "
-                                    "(M=%d H=%d K=%d)", plan->M, H, K);
-  if (planes && K > 1 && plane_stride < int64_t(N) * plan->M * H)
-    return fail(CG_ERR_ARG, "lstm_hconv_step: plane stride %lld < N*M*H", (long long)plane_stride);
-  // the kernel moves h_prev and the planes as float4
-  if ((reinterpret_cast<uintptr_t>(h_prev) & 15) || (planes && (reinterpret_cast<uintptr_t>(planes) & 15)) ||
-      (planes && K > 1 && (plane_stride & 3)))
-    return fail(CG_ERR_ARG, "lstm_hconv_step: h_prev / planes must be 16-byte aligned and the "
-                            "plane stride a multiple of 4 floats");
-  const void* outs[] = {c_out, h_out, act, planes};
-  const void* ins[] = {h_prev, c_prev, gx};
-  for (const void* o : outs)
-    for (const void* i : ins)
-      if (o && o == i) return fail(CG_ERR_ARG, "lstm_hconv_step: outputs must not alias inputs");
-  if ((rc = check_device(plan))) return rc;
-  CG_HIP(cg::launch_lstm_hstep(gates, N, plan->M, K, plan->rowptr, plan->col, plan->val, h_prev,
-                               c_prev, gx, Wh, bias, c_out, h_out, act, planes, plane_stride,
-                               reinterpret_cast<hipStream_t>(stream)));
-  return ok();
-}
-
-static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-int cg_lstm_seq_supported(const cg_plan* plan, int32_t H, int32_t K, int32_t* supported) {
-  if (!plan || !supported) return fail(CG_ERR_ARG, "lstm_seq_supported: null argument");
-  *supported =
-      (cg::lstm_seq_ok(plan->M, H, K, plan->nnz) && cg::lstm_bstep_ok(plan->M, H, K, plan->nnzT)) ? 1 : 0;
-  return ok();
-}
-
-int cg_lstm_seq_x_supported(const cg_plan* plan, int32_t Fin, int32_t H, int32_t K, int32_t* supported) {
-  if (!plan || !supported) return fail(CG_ERR_ARG, "lstm_seq_x_supported: null argument");
-  *supported = (Fin >= 1 && Fin <= 8 && cg::lstm_seq_ok(plan->M, H, K, plan->nnz, Fin) &&
-                cg::lstm_bstep_ok(plan->M, H, K, plan->nnzT)) ? 1 : 0;
-  return ok();
-}
-
-int cg_lstm_seq_workspace_bytes(const cg_plan* plan, int32_t N, size_t* bytes) {
-  if (!plan || !bytes || N < 1) return fail(CG_ERR_ARG, "lstm_seq_workspace_bytes: bad arguments");
-  *bytes = al256(sizeof(int) * size_t(2) * cg::lstm_seq_pairs(N, plan->device));
-  return ok();
-}
-
-static int lstm_seq_impl(cg_plan* plan, int32_t T, int32_t N, int32_t H, int32_t K, int32_t gates,
-                         const float* gx, const float* xs, const float* Wx, int32_t Fin,
-                         float* xplanes, int64_t xplane_stride, const float* Wh, const float* bias,
-                         const float* h0, const float* c0, float* hs, float* cs, float* act,
-                         float* planes, int64_t plane_stride, void* workspace, size_t ws_bytes,
-                         void* stream) {
-  int rc = check_lstm(int64_t(T) * N * (plan ? plan->M : 1), H, gates);
-  if (rc) return rc;
-  if (!plan || T < 1 || N < 1 || K < 1) return fail(CG_ERR_ARG, "lstm_seq_forward: bad plan / T / N / K");
-  if ((!gx && !xs) || !Wh || !hs || !cs) return fail(CG_ERR_ARG, "lstm_seq_forward: null gx|xs / Wh / hs / cs");
-  if (xs && (Fin < 1 || Fin > 8 || !Wx || !xplanes))
-    return fail(CG_ERR_ARG, "lstm_seq_forward_x: needs 1 <= feat_in <= 8, Wx and the x planes");
-  if (!cg::lstm_seq_ok(plan->M, H, K, plan->nnz, xs ? Fin : 0))
-    return fail(CG_ERR_UNSUPPORTED, "lstm_seq_forward: needs H = 32, M <= 1024 and L~ plus the "
-                                    "weights in LDS (M=%d nnz=%lld H=%d K=%d)",
-                plan->M, (long long)plan->nnz, H, K);
-  const int64_t R = int64_t(T) * N * plan->M;
-  if (!planes && K > 1)
-    return fail(CG_ERR_ARG, "lstm_seq_forward: planes are required for K > 1 (the pair hands "
-                            "its quarters' Chebyshev orders to the partner through them)");
-  if (planes && K > 1 && plane_stride < R * H)
-    return fail(CG_ERR_ARG, "lstm_seq_forward: plane stride %lld < T*N*M*H", (long long)plane_stride);
-  if (xs && xplane_stride < R * Fin)
-    return fail(CG_ERR_ARG, "lstm_seq_forward_x: x plane stride %lld < T*N*M*feat_in",
-                (long long)xplane_stride);
-  if ((gx && !al16(gx)) || !al16(hs) || !al16(cs) || (act && !al16(act)) || (planes && !al16(planes)) ||
-      (h0 && !al16(h0)) || (c0 && !al16(c0)) || (bias && !al16(bias)) ||
-      (planes && K > 1 && (plane_stride & 3)))
-    return fail(CG_ERR_ARG, "lstm_seq_forward: tensors must be 16-byte aligned (float4 access), "
-                            "plane stride a multiple of 4");
-  const void* outs[] = {hs, cs, act, planes, xplanes};
-  const void* ins[] = {gx, xs, Wx, Wh, bias, h0, c0};
-  for (const void* o : outs)
-    for (const void* i : ins)
-      if (o && o == i) return fail(CG_ERR_ARG, "lstm_seq_forward: outputs must not alias inputs");
-  size_t need = 0;
-  if ((rc = cg_lstm_seq_workspace_bytes(plan, N, &need))) return rc;
-  if (!workspace || ws_bytes < need)
-    return fail(CG_ERR_ARG, "lstm_seq_forward: workspace %zu < %zu bytes", ws_bytes, need);
-  if ((rc = check_device(plan))) return rc;
-  const int P = cg::lstm_seq_pairs(N, plan->device);
-  int* flags = static_cast<int*>(workspace);
-  if (!plan->seq_fault) {
-    void* hp = nullptr;
-    CG_HIP(hipHostMalloc(&hp, 64, hipHostMallocMapped | hipHostMallocCoherent));
-    plan->seq_fault = static_cast<int*>(hp);
-    *plan->seq_fault = 0;
-    void* dp = nullptr;
-    CG_HIP(hipHostGetDevicePointer(&dp, hp, 0));
-    plan->seq_fault_dev = static_cast<int*>(dp);
-    CG_HIP(hipEventCreateWithFlags(&plan->seq_event, hipEventDisableTiming));
-  }
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  CG_HIP(cg::launch_lstm_seq(gates, T, N, plan->M, K, plan->nnz, plan->rowptr, plan->col, plan->val,
-                             plan->lorder, xs, Wx, Fin, xplanes, xplane_stride, gx, Wh, bias, h0,
-                             c0, hs, cs, act, planes, plane_stride, flags, plan->seq_fault_dev, P, s,
-                             plan->seq_fault_test, plan->max_row_nnz));
-  CG_HIP(hipEventRecord(plan->seq_event, s));
-  plan->seq_launched = true;
-  return ok();
-}
-
-int cg_lstm_seq_forward(cg_plan* plan, int32_t T, int32_t N, int32_t H, int32_t K, int32_t gates,
-                        const float* gx, const float* Wh, const float* bias, const float* h0,
-                        const float* c0, float* hs, float* cs, float* act, float* planes,
-                        int64_t plane_stride, void* workspace, size_t ws_bytes, void* stream) {
-  return lstm_seq_impl(plan, T, N, H, K, gates, gx, nullptr, nullptr, 0, nullptr, 0, Wh, bias, h0,
-                       c0, hs, cs, act, planes, plane_stride, workspace, ws_bytes, stream);
-}
-
-int cg_lstm_seq_forward_x(cg_plan* plan, int32_t T, int32_t N, int32_t Fin, int32_t H, int32_t K,
-                          int32_t gates, const float* xs, const float* Wx, float* xplanes,
-                          int64_t xplane_stride, const float* Wh, const float* bias,
-                          const float* h0, const float* c0, float* hs, float* cs, float* act,
-                          float* planes, int64_t plane_stride, void* workspace, size_t ws_bytes,
-                          void* stream) {
-  if (!xs) return fail(CG_ERR_ARG, "lstm_seq_forward_x: null xs");
-  return lstm_seq_impl(plan, T, N, H, K, gates, nullptr, xs, Wx, Fin, xplanes, xplane_stride, Wh,
-                       bias, h0, c0, hs, cs, act, planes, plane_stride, workspace, ws_bytes, stream);
-}
-
-int cg_lstm_seq_fault(cg_plan* plan, int32_t wait, int32_t clear, int32_t* fault) {
-  if (!plan || !fault) return fail(CG_ERR_ARG, "lstm_seq_fault: null argument");
-  *fault = 0;
-  if (!plan->seq_launched) return ok();
-  if (wait) {
-    CG_HIP(hipEventSynchronize(plan->seq_event));
-  } else {
-    const hipError_t q = hipEventQuery(plan->seq_event);
-    if (q == hipErrorNotReady) {
-      *fault = -1;  // the last sequence launch is still in flight
-      return ok();
-    }
-    if (q != hipSuccess) return fail(CG_ERR_HIP, "lstm_seq_fault: %s", hipGetErrorString(q));
-  }
-  const int v = __atomic_load_n(plan->seq_fault, __ATOMIC_ACQUIRE);
-  if (!v) return ok();
-  *fault = 1;
-  if (clear) __atomic_store_n(plan->seq_fault, 0, __ATOMIC_RELEASE);
-  return fail(CG_ERR_HIP, "lstm_seq_forward: a workgroup pair hand-off timed out (a partner "
-                          "workgroup was not co-resident); the launch's hs / cs / act hold NaN "
-                          "from the lost step on");
-}
-
-int cg_lstm_seq_status(const cg_plan* plan, int32_t N, const void* workspace, int32_t* status,
-                       void* stream) {
-  if (!plan || !status || N < 1) return fail(CG_ERR_ARG, "lstm_seq_status: bad arguments");
-  (void)workspace;  // the fault word lives in the plan (sticky), not in the workspace
-  CG_HIP(hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)));
-  return cg_lstm_seq_fault(const_cast<cg_plan*>(plan), 1, 0, status);
-}
-
-int cg_plan_set_seq_fault_test(cg_plan* plan, int32_t step) {
-  if (!plan || step < -1) return fail(CG_ERR_ARG, "plan_set_seq_fault_test: bad arguments");
-  plan->seq_fault_test = step;
-  return ok();
-}
-
 int cg_plan_query_stream_dispatch(const cg_plan* plan, int32_t N, int32_t Fin, int32_t K,
                                   int32_t Fout, int layout, int32_t out[16]) {
   int rc = check_shape(plan, N, Fin, K, Fout);
@@ -1757,112 +1208,6 @@ int cg_plan_query_stream_dispatch(const cg_plan* plan, int32_t N, int32_t Fin, i
     return fail(CG_ERR_UNSUPPORTED, "not on the streaming path: M=%d Fin=%d K=%d Fout=%d", plan->M,
                 Fin, K, Fout);
   stream_dispatch(r, out);
-  return ok();
-}
-
-int cg_lstm_bwd_step(cg_plan* plan, int32_t N, int32_t H, int32_t K, int32_t gates, const float* dh,
-                     const float* dh_rec, const float* dc, const float* act,
-                     int32_t act_unit_major, const float* c_prev, const float* c_out,
-                     const float* Wh, float* dpre, float* dc_prev, float* dh_prev, void* stream) {
-  int rc = check_lstm(int64_t(N) * (plan ? plan->M : 1), H, gates);
-  if (rc) return rc;
-  if (!plan || N < 1 || K < 1) return fail(CG_ERR_ARG, "lstm_bwd_step: bad plan / N / K");
-  if (!act || !c_out || !Wh || !dpre)
-    return fail(CG_ERR_ARG, "lstm_bwd_step: null act / c_out / Wh / dpre");
-  if (!cg::lstm_bstep_ok(plan->M, H, K, plan->nnzT))
-    return fail(CG_ERR_UNSUPPORTED, "lstm_bwd_step: needs H = 32, M <= 1024, K <= 4 (M=%d H=%d K=%d)",
-                plan->M, H, K);
-  const void* all[] = {dh, dh_rec, dc, act, c_prev, c_out, dpre, dc_prev, dh_prev};
-  for (const void* p : all)
-    if (p && !al16(p)) return fail(CG_ERR_ARG, "lstm_bwd_step: tensors must be 16-byte aligned");
-  const void* outs[] = {dpre, dc_prev, dh_prev};
-  const void* ins[] = {dh, dh_rec, dc, act, c_prev, c_out, Wh};
-  for (const void* o : outs)
-    for (const void* i : ins)
-      if (o && o == i) return fail(CG_ERR_ARG, "lstm_bwd_step: outputs must not alias inputs");
-  if ((rc = check_device(plan))) return rc;
-  if (!dh_prev) {  // no h-conv at this step (a zero-state layer's step 0): the pointwise part
-    CG_HIP(cg::launch_lstm_bwd(gates, int64_t(N) * plan->M, H, dh, dh_rec, dc, act, c_prev, c_out,
-                               dpre, dc_prev, reinterpret_cast<hipStream_t>(stream),
-                               act_unit_major));
-    return ok();
-  }
-  CG_HIP(cg::launch_lstm_bstep(gates, N, plan->M, K, plan->trowptr, plan->tcol, plan->tval,
-                               plan->tlorder, plan->nnzT, dh, dh_rec,
-                               dc, act, act_unit_major, c_prev, c_out, Wh, dpre, dc_prev, dh_prev,
-                               reinterpret_cast<hipStream_t>(stream)));
-  return ok();
-}
-
-int cg_perm_gather(const float* x, const int32_t* perm, int32_t N, int32_t M_in, int32_t M_out,
-                   int32_t F, float* out, void* stream) {
-  if (!x || !perm || !out || N < 1 || M_in < 1 || M_out < 1 || F < 1)
-    return fail(CG_ERR_ARG, "perm_gather: bad arguments");
-  CG_HIP(cg::launch_perm_gather(x, perm, N, M_in, M_out, F, out,
-                                reinterpret_cast<hipStream_t>(stream)));
-  return ok();
-}
-
-int cg_maxpool_forward(const float* x, int32_t N, int32_t M, int32_t F, int32_t p, float* y,
-                       int32_t* argmax, void* stream) {
-  if (!x || !y || N < 1 || M < 1 || F < 1 || p < 1 || M % p)
-    return fail(CG_ERR_ARG, "maxpool_forward: bad arguments (M=%d p=%d)", M, p);
-  CG_HIP(cg::launch_maxpool_fwd(x, N, M, F, p, y, argmax, reinterpret_cast<hipStream_t>(stream)));
-  return ok();
-}
-
-int cg_maxpool_backward(const float* dy, const int32_t* argmax, int32_t N, int32_t M, int32_t F,
-                        int32_t p, float* dx, void* stream) {
-  if (!dy || !argmax || !dx || N < 1 || M < 1 || F < 1 || p < 1 || M % p)
-    return fail(CG_ERR_ARG, "maxpool_backward: bad arguments (M=%d p=%d)", M, p);
-  CG_HIP(cg::launch_maxpool_bwd(dy, argmax, N, M, F, p, dx, reinterpret_cast<hipStream_t>(stream)));
-  return ok();
-}
-
-int cg_avgpool_forward(const float* x, int32_t N, int32_t M, int32_t F, int32_t p, float* y,
-                       void* stream) {
-  if (!x || !y || N < 1 || M < 1 || F < 1 || p < 1 || M % p)
-    return fail(CG_ERR_ARG, "avgpool_forward: bad arguments (M=%d p=%d)", M, p);
-  CG_HIP(cg::launch_avgpool_fwd(x, N, M, F, p, y, reinterpret_cast<hipStream_t>(stream)));
-  return ok();
-}
-
-int cg_avgpool_backward(const float* dy, int32_t N, int32_t M, int32_t F, int32_t p, float* dx,
-                        void* stream) {
-  if (!dy || !dx || N < 1 || M < 1 || F < 1 || p < 1 || M % p)
-    return fail(CG_ERR_ARG, "avgpool_backward: bad arguments (M=%d p=%d)", M, p);
-  CG_HIP(cg::launch_avgpool_bwd(dy, N, M, F, p, dx, reinterpret_cast<hipStream_t>(stream)));
-  return ok();
-}
-
-int cg_adam_update(float* param, const float* grad, float* m, float* v, int64_t n, float lr,
-                   float beta1, float beta2, float eps, int32_t step, float grad_scale,
-                   void* stream) {
-  if (!param || !grad || !m || !v || n < 0 || step < 1)
-    return fail(CG_ERR_ARG, "adam_update: bad arguments");
-  if (n == 0) return ok();
-  const double lr_t =
-      double(lr) * std::sqrt(1.0 - std::pow(double(beta2), step)) / (1.0 - std::pow(double(beta1), step));
-  CG_HIP(cg::launch_adam(param, grad, m, v, n, float(lr_t), beta1, beta2, eps, grad_scale,
-                         reinterpret_cast<hipStream_t>(stream)));
-  return ok();
-}
-
-int cg_sgd_update(float* param, const float* grad, int64_t n, float lr, float grad_scale,
-                  void* stream) {
-  if (!param || !grad || n < 0) return fail(CG_ERR_ARG, "sgd_update: bad arguments");
-  if (n == 0) return ok();
-  CG_HIP(cg::launch_sgd(param, grad, n, lr, grad_scale, reinterpret_cast<hipStream_t>(stream)));
-  return ok();
-}
-
-int cg_rmsprop_update(float* param, const float* grad, float* ms, float* mom, int64_t n, float lr,
-                      float rho, float momentum, float eps, float grad_scale, void* stream) {
-  if (!param || !grad || !ms || !mom || n < 0 || !(eps > 0.f))
-    return fail(CG_ERR_ARG, "rmsprop_update: bad arguments");
-  if (n == 0) return ok();
-  CG_HIP(cg::launch_rmsprop(param, grad, ms, mom, n, lr, rho, momentum, eps, grad_scale,
-                            reinterpret_cast<hipStream_t>(stream)));
   return ok();
 }
 

@@ -5,10 +5,12 @@
 
 #include <hip/hip_runtime.h>
 
+#include "abi_checks.h"
 #include "cg_internal.h"
 
 using cg::al256;
 using cg::fail;
+using cg::need_ws;
 using cg::ok;
 
 extern "C" {
@@ -40,8 +42,7 @@ int cg_fourier_forward(int32_t N, int32_t M, int32_t Fin, int32_t Fout, const fl
   if (!fourier_shape_ok(N, M, Fin, Fout)) return fail(CG_ERR_ARG, "fourier_forward: bad shape");
   size_t need;
   fourier_ws(N, M, Fin, Fout, &need, nullptr);
-  if (ws_bytes < need || (need && !workspace))
-    return fail(CG_ERR_ARG, "fourier_forward workspace too small: %zu < %zu", ws_bytes, need);
+  if (int rc = need_ws("fourier_forward", workspace, ws_bytes, need)) return rc;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   char* w = static_cast<char*>(workspace);
   const size_t xin = size_t(N) * Fin * M * 4, yout = size_t(N) * Fout * M * 4;
@@ -71,8 +72,7 @@ int cg_fourier_backward(int32_t N, int32_t M, int32_t Fin, int32_t Fout, const f
   if (!fourier_shape_ok(N, M, Fin, Fout)) return fail(CG_ERR_ARG, "fourier_backward: bad shape");
   size_t need;
   fourier_ws(N, M, Fin, Fout, nullptr, &need);
-  if (!workspace || ws_bytes < need)
-    return fail(CG_ERR_ARG, "fourier_backward workspace too small: %zu < %zu", ws_bytes, need);
+  if (int rc = need_ws("fourier_backward", workspace, ws_bytes, need)) return rc;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   char* w = static_cast<char*>(workspace);
   const size_t xin = size_t(N) * Fin * M * 4, yout = size_t(N) * Fout * M * 4;
@@ -106,7 +106,7 @@ static int check_gft(const char* what, int32_t N, int32_t M, int32_t C, const vo
   if (int64_t(N) * M * C >= (int64_t(1) << 31))
     return fail(CG_ERR_ARG, "%s: N*M*C = %lld exceeds 2^31", what, (long long)(int64_t(N) * M * C));
   if (!basis) return fail(CG_ERR_ARG, "%s: null basis", what);
-  if (basis_bytes < cg::gft_basis_bytes(M) || (reinterpret_cast<uintptr_t>(basis) & 15))
+  if (basis_bytes < cg::gft_basis_bytes(M) || !cg::al16(basis))
     return fail(CG_ERR_ARG, "%s: basis too small or not 16-byte aligned: %zu < %zu", what, basis_bytes,
                 cg::gft_basis_bytes(M));
   return CG_OK;
@@ -186,8 +186,7 @@ int cg_flstm_step(int32_t N, int32_t M, int32_t H, int32_t gates, const void* ba
   if (!ghat_x || !c_out || !h_out) return fail(CG_ERR_ARG, "flstm_step: null ghat_x / c_out / h_out");
   if (h_prev && (!Wh || !hhat)) return fail(CG_ERR_ARG, "flstm_step: h_prev needs Wh and hhat");
   const size_t need = flstm_ws(N, M, H);
-  if (h_prev && (!workspace || ws_bytes < need))
-    return fail(CG_ERR_ARG, "flstm_step workspace too small: %zu < %zu", ws_bytes, need);
+  if (h_prev && (rc = need_ws("flstm_step", workspace, ws_bytes, need))) return rc;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const bool x3 = cg::option(cg::kOptGemmX3) != 0;
   const float* ghat = ghat_x;
@@ -252,8 +251,7 @@ static int fres_forward_impl(const char* what, int32_t N, int32_t M, int32_t Fin
   if ((rc = check_act(what, act))) return rc;
   size_t need;
   fres_ws(N, M, Fin, Fout, &need, nullptr);
-  if (!workspace || ws_bytes < need)
-    return fail(CG_ERR_ARG, "%s workspace too small: %zu < %zu", what, ws_bytes, need);
+  if ((rc = need_ws(what, workspace, ws_bytes, need))) return rc;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const bool x3 = cg::option(cg::kOptGemmX3) != 0;
   float* yhat = static_cast<float*>(workspace);
@@ -281,8 +279,7 @@ static int fres_backward_impl(const char* what, int32_t N, int32_t M, int32_t Fi
   size_t yout, need;  // the forward's size is ghat's, so dxhat's offset
   fres_ws(N, M, Fin, Fout, &yout, &need);
   if (!dx) need = yout;  // no dxhat
-  if (!workspace || ws_bytes < need)
-    return fail(CG_ERR_ARG, "%s workspace too small: %zu < %zu", what, ws_bytes, need);
+  if ((rc = need_ws(what, workspace, ws_bytes, need))) return rc;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const bool x3 = cg::option(cg::kOptGemmX3) != 0;
   float* ghat = static_cast<float*>(workspace);

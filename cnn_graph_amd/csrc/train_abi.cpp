@@ -1,0 +1,302 @@
+// C ABI of the training ops (see include/cheb_mi355.h): loss, dropout, clip,
+// seq_xent, slice and stack, weight and bias gradients, bias_act, gemm, pooling,
+// perm and the optimizers -- argument validation and the launches.
+#include "../../include/cheb_mi355.h"
+
+#include <hip/hip_runtime.h>
+
+#include "abi_checks.h"
+#include "cg_internal.h"
+
+using cg::al256;
+using cg::dw_slab_bytes;
+using cg::fail;
+using cg::need_ws;
+using cg::ok;
+
+extern "C" {
+
+int cg_mse_loss_workspace_bytes(int64_t n, size_t* bytes) {
+  if (!bytes || n < 1) return fail(CG_ERR_ARG, "mse_loss: bad arguments");
+  *bytes = al256(size_t(cg::mse_chunks(n)) * 4);
+  return ok();
+}
+
+int cg_mse_loss(const float* pred, const float* labels, int64_t n, float* loss, float* dpred,
+                void* workspace, size_t ws_bytes, void* stream) {
+  if (!pred || !labels || !loss || n < 1) return fail(CG_ERR_ARG, "mse_loss: bad arguments");
+  if (int rc = need_ws("mse_loss", workspace, ws_bytes, al256(size_t(cg::mse_chunks(n)) * 4)))
+    return rc;
+  CG_HIP(cg::launch_mse(pred, labels, n, static_cast<float*>(workspace), loss, dpred,
+                        reinterpret_cast<hipStream_t>(stream)));
+  return ok();
+}
+
+int cg_mse_loss_ema(const float* pred, const float* labels, int64_t n, float* loss, float* dpred,
+                    float* ema, float decay, void* workspace, size_t ws_bytes, void* stream) {
+  if (!pred || !labels || !loss || !ema || n < 1 || !(decay >= 0.f && decay <= 1.f))
+    return fail(CG_ERR_ARG, "mse_loss_ema: bad arguments");
+  if (int rc = need_ws("mse_loss_ema", workspace, ws_bytes, al256(size_t(cg::mse_chunks(n)) * 4)))
+    return rc;
+  CG_HIP(cg::launch_mse(pred, labels, n, static_cast<float*>(workspace), loss, dpred,
+                        reinterpret_cast<hipStream_t>(stream), ema, decay));
+  return ok();
+}
+
+int cg_dropout_forward(const float* x, int64_t n, float keep_prob, uint64_t seed, float* y,
+                       void* stream) {
+  if (!x || !y || n < 1 || !(keep_prob > 0.f && keep_prob <= 1.f))
+    return fail(CG_ERR_ARG, "dropout_forward: bad arguments (keep_prob=%g)", keep_prob);
+  CG_HIP(cg::launch_dropout(x, y, n, keep_prob, seed, 0, reinterpret_cast<hipStream_t>(stream)));
+  return ok();
+}
+
+int cg_dropout_backward(const float* dy, int64_t n, float keep_prob, uint64_t seed, float* dx,
+                        void* stream) {
+  if (!dy || !dx || n < 1 || !(keep_prob > 0.f && keep_prob <= 1.f))
+    return fail(CG_ERR_ARG, "dropout_backward: bad arguments (keep_prob=%g)", keep_prob);
+  CG_HIP(cg::launch_dropout(dy, dx, n, keep_prob, seed, 1, reinterpret_cast<hipStream_t>(stream)));
+  return ok();
+}
+
+int cg_clip_by_norm(float* t, int64_t n, float clip_norm, int32_t* nonfinite, void* stream) {
+  if (!t || n < 1 || !(clip_norm > 0.f))
+    return fail(CG_ERR_ARG, "clip_by_norm: bad arguments (n=%lld, clip_norm=%g)", (long long)n,
+                clip_norm);
+  CG_HIP(cg::launch_clip_norm(t, n, clip_norm, nonfinite, reinterpret_cast<hipStream_t>(stream)));
+  return ok();
+}
+
+int cg_seq_xent_workspace_bytes(int32_t T, int32_t N, int32_t M, int32_t H, size_t* out) {
+  if (!out || T < 1 || N < 1 || M < 1 || H < 1 || int64_t(T) * N > INT32_MAX)
+    return fail(CG_ERR_ARG, "seq_xent_workspace_bytes: bad arguments");
+  if (H > 256) return fail(CG_ERR_UNSUPPORTED, "seq_xent: H = %d, the head supports H <= 256", H);
+  *out = al256(cg::seq_xent_ws_bytes(int64_t(T) * N, M, H));
+  return ok();
+}
+
+int cg_seq_xent_head(const float* hs, const float* w, const float* b, const int32_t* labels,
+                     int32_t T, int32_t N, int32_t M, int32_t H, float keep, uint64_t seed,
+                     float loss_scale, float* logits, float* ce, float* loss, float* dhs, float* dw,
+                     float* db, void* ws, size_t ws_bytes, void* stream) {
+  if (!hs || !w || !b || !labels || !loss || (dhs && (!dw || !db)))
+    return fail(CG_ERR_ARG, "seq_xent_head: null pointer");
+  if (T < 1 || N < 1 || M < 1 || H < 1 || int64_t(T) * N > INT32_MAX)
+    return fail(CG_ERR_ARG, "seq_xent_head: bad sizes (T=%d N=%d M=%d H=%d)", T, N, M, H);
+  if (!(keep > 0.f && keep <= 1.f))
+    return fail(CG_ERR_ARG, "seq_xent_head: keep = %g outside (0, 1]", keep);
+  if (H > 256) return fail(CG_ERR_UNSUPPORTED, "seq_xent: H = %d, the head supports H <= 256", H);
+  const size_t need = al256(cg::seq_xent_ws_bytes(int64_t(T) * N, M, H));
+  if (int rc = need_ws("seq_xent_head", ws, ws_bytes, need)) return rc;
+  CG_HIP(cg::launch_seq_xent(hs, w, b, labels, T, N, M, H, keep, seed, loss_scale, logits, ce, loss,
+                             dhs, dw, db, static_cast<float*>(ws),
+                             reinterpret_cast<hipStream_t>(stream)));
+  return ok();
+}
+
+int cg_slice_channels(const float* x, int64_t rows, int32_t C, int32_t c0, int32_t c1, float* out,
+                      void* stream) {
+  if (!x || !out || rows < 1 || C < 1 || c0 < 0 || c1 <= c0 || c1 > C)
+    return fail(CG_ERR_ARG, "slice_channels: bad arguments (C=%d, [%d, %d))", C, c0, c1);
+  CG_HIP(cg::launch_slice_channels(x, rows, C, c0, c1, out, reinterpret_cast<hipStream_t>(stream)));
+  return ok();
+}
+
+int cg_stack_merge_forward(int32_t N, int32_t M, int32_t F, const float* out_i, const float* w_i,
+                           int32_t accumulate, float* y, void* stream) {
+  if (N < 1 || M < 1 || F < 1 || !out_i || !w_i || !y)
+    return fail(CG_ERR_ARG, "stack_merge_forward: bad arguments");
+  if (out_i == y) return fail(CG_ERR_ARG, "stack_merge_forward: y must not alias out_i");
+  CG_HIP(cg::launch_stack_merge_fwd(out_i, w_i, N, int64_t(M) * F, accumulate, y,
+                                    reinterpret_cast<hipStream_t>(stream)));
+  return ok();
+}
+
+int cg_stack_merge_backward(int32_t N, int32_t M, int32_t F, const float* dy, const float* out_i,
+                            const float* w_i, float* dout_i, float* dw_i, void* stream) {
+  if (N < 1 || M < 1 || F < 1 || !dy || !out_i || !w_i || (!dout_i && !dw_i))
+    return fail(CG_ERR_ARG, "stack_merge_backward: bad arguments");
+  if (dout_i && (dout_i == out_i || dout_i == dy))
+    return fail(CG_ERR_ARG, "stack_merge_backward: dout_i must not alias dy / out_i");
+  CG_HIP(cg::launch_stack_merge_bwd(dy, out_i, w_i, N, int64_t(M) * F, dout_i, dw_i,
+                                    reinterpret_cast<hipStream_t>(stream)));
+  return ok();
+}
+
+int cg_weight_grad_workspace_bytes(int64_t R, int32_t FinK, int32_t Fout, size_t* bytes) {
+  if (!bytes || R < 1 || FinK < 1 || Fout < 1) return fail(CG_ERR_ARG, "weight_grad: bad arguments");
+  *bytes = dw_slab_bytes(R, 0, FinK, Fout);
+  return ok();
+}
+
+int cg_weight_grad(int64_t R, int32_t FinK, int32_t Fout, const float* basis, const float* dy,
+                   float* dW, int32_t accumulate, void* workspace, size_t ws_bytes, void* stream) {
+  if (!basis || !dy || !dW || R < 1 || FinK < 1 || Fout < 1)
+    return fail(CG_ERR_ARG, "weight_grad: bad arguments");
+  if (int rc = need_ws("weight_grad", workspace, ws_bytes, dw_slab_bytes(R, 0, FinK, Fout))) return rc;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  float* slabs = static_cast<float*>(workspace);
+  CG_HIP(cg::launch_dw_slabs(basis, dy, R, FinK, Fout, slabs, s));
+  CG_HIP(cg::launch_reduce_slabs_acc(slabs, cg::dw_chunks(R), int64_t(FinK) * Fout, dW,
+                                     accumulate != 0, s));
+  return ok();
+}
+
+int cg_weight_grad_planes(int64_t R, int32_t Fin, int32_t K, int32_t Fout, const float* planes,
+                          int64_t plane_stride, const float* dy, float* dW, int32_t accumulate,
+                          void* workspace, size_t ws_bytes, void* stream) {
+  if (!planes || !dy || !dW || R < 1 || Fin < 1 || K < 1 || Fout < 1 || plane_stride < R * Fin)
+    return fail(CG_ERR_ARG, "weight_grad_planes: bad arguments");
+  const int FinK = Fin * K;
+  if (int rc = need_ws("weight_grad_planes", workspace, ws_bytes, dw_slab_bytes(R, 0, FinK, Fout)))
+    return rc;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  float* slabs = static_cast<float*>(workspace);
+  CG_HIP(cg::launch_dw_slabs(planes, dy, R, FinK, Fout, slabs, s, Fin, plane_stride, K));
+  CG_HIP(cg::launch_reduce_slabs_acc(slabs, cg::dw_chunks(R), int64_t(FinK) * Fout, dW,
+                                     accumulate != 0, s));
+  return ok();
+}
+
+int cg_bias_grad_workspace_bytes(int64_t R, int32_t C, size_t* bytes) {
+  if (!bytes || R < 1 || C < 1) return fail(CG_ERR_ARG, "bias_grad: bad arguments");
+  *bytes = cg::colsum_ws_bytes(R, C);
+  return ok();
+}
+
+int cg_bias_grad(int64_t R, int32_t C, const float* dy, float* db, int32_t accumulate,
+                 void* workspace, size_t ws_bytes, void* stream) {
+  if (!dy || !db || R < 1 || C < 1) return fail(CG_ERR_ARG, "bias_grad: bad arguments");
+  if (int rc = need_ws("bias_grad", workspace, ws_bytes, cg::colsum_ws_bytes(R, C))) return rc;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  float* slabs = static_cast<float*>(workspace);
+  CG_HIP(cg::launch_colsum_slabs(dy, R, C, slabs, s));
+  CG_HIP(cg::launch_reduce_slabs_acc(slabs, cg::colsum_chunks(R), C, db, accumulate != 0, s));
+  return ok();
+}
+
+// ---- bias + activation (b1relu / b1tanh / b2relu) and fc GEMM -----------------
+int cg_bias_act_forward(int64_t n, int32_t bias_len, const float* x, const float* bias,
+                        int32_t act, float* y, void* stream) {
+  if (!x || !y || n < 1) return fail(CG_ERR_ARG, "bias_act_forward: bad arguments");
+  if (act < CG_ACT_NONE || act > CG_ACT_TANH) return fail(CG_ERR_ARG, "unknown activation %d", act);
+  if (bias && (bias_len < 1 || n % bias_len))
+    return fail(CG_ERR_ARG, "bias_act_forward: n=%lld is not a multiple of bias_len=%d",
+                (long long)n, bias_len);
+  CG_HIP(cg::launch_bias_act_fwd(x, bias, bias ? bias_len : 1, act, n, y,
+                                 reinterpret_cast<hipStream_t>(stream)));
+  return ok();
+}
+
+int cg_bias_act_workspace_bytes(int64_t n, int32_t bias_len, size_t* bytes) {
+  if (!bytes || n < 1 || bias_len < 1 || n % bias_len)
+    return fail(CG_ERR_ARG, "bias_act_workspace_bytes: bad arguments");
+  *bytes = cg::colsum_ws_bytes(n / bias_len, bias_len);
+  return ok();
+}
+
+int cg_bias_act_backward(int64_t n, int32_t bias_len, const float* dy, const float* y, int32_t act,
+                         float* dz, float* db, int32_t accumulate, void* workspace,
+                         size_t ws_bytes, void* stream) {
+  if (!dy || !dz || n < 1) return fail(CG_ERR_ARG, "bias_act_backward: bad arguments");
+  if (act < CG_ACT_NONE || act > CG_ACT_TANH) return fail(CG_ERR_ARG, "unknown activation %d", act);
+  if (act != CG_ACT_NONE && !y) return fail(CG_ERR_ARG, "bias_act_backward: activation needs y");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  CG_HIP(cg::launch_bias_act_bwd(dy, y, act, n, dz, s));
+  if (!db) return ok();
+  if (bias_len < 1 || n % bias_len)
+    return fail(CG_ERR_ARG, "bias_act_backward: n=%lld is not a multiple of bias_len=%d",
+                (long long)n, bias_len);
+  const int64_t R = n / bias_len;
+  if (int rc = need_ws("bias_act", workspace, ws_bytes, cg::colsum_ws_bytes(R, bias_len))) return rc;
+  float* slabs = static_cast<float*>(workspace);
+  CG_HIP(cg::launch_colsum_slabs(dz, R, bias_len, slabs, s));
+  CG_HIP(cg::launch_reduce_slabs_acc(slabs, cg::colsum_chunks(R), bias_len, db, accumulate != 0, s));
+  return ok();
+}
+
+int cg_gemm_f32(int32_t trans_a, int32_t trans_b, int32_t M, int32_t N, int32_t K, const float* A,
+                int32_t lda, const float* B, int32_t ldb, float* C, int32_t ldc, void* stream) {
+  if (!A || !B || !C || M < 1 || N < 1 || K < 1) return fail(CG_ERR_ARG, "gemm_f32: bad arguments");
+  if (lda < (trans_a ? M : K) || ldb < (trans_b ? K : N) || ldc < N)
+    return fail(CG_ERR_ARG, "gemm_f32: leading dimension too small (lda=%d ldb=%d ldc=%d)", lda, ldb,
+                ldc);
+  if ((M + 63) / 64 > 2147483647 / 2 || (N + 63) / 64 > 65535)
+    return fail(CG_ERR_ARG, "gemm_f32: N=%d too large for the grid", N);
+  CG_HIP(cg::launch_gemm_f32(trans_a != 0, trans_b != 0, M, N, K, A, lda, B, ldb, C, ldc, 1,
+                             reinterpret_cast<hipStream_t>(stream)));
+  return ok();
+}
+
+int cg_perm_gather(const float* x, const int32_t* perm, int32_t N, int32_t M_in, int32_t M_out,
+                   int32_t F, float* out, void* stream) {
+  if (!x || !perm || !out || N < 1 || M_in < 1 || M_out < 1 || F < 1)
+    return fail(CG_ERR_ARG, "perm_gather: bad arguments");
+  CG_HIP(cg::launch_perm_gather(x, perm, N, M_in, M_out, F, out,
+                                reinterpret_cast<hipStream_t>(stream)));
+  return ok();
+}
+
+int cg_maxpool_forward(const float* x, int32_t N, int32_t M, int32_t F, int32_t p, float* y,
+                       int32_t* argmax, void* stream) {
+  if (!x || !y || N < 1 || M < 1 || F < 1 || p < 1 || M % p)
+    return fail(CG_ERR_ARG, "maxpool_forward: bad arguments (M=%d p=%d)", M, p);
+  CG_HIP(cg::launch_maxpool_fwd(x, N, M, F, p, y, argmax, reinterpret_cast<hipStream_t>(stream)));
+  return ok();
+}
+
+int cg_maxpool_backward(const float* dy, const int32_t* argmax, int32_t N, int32_t M, int32_t F,
+                        int32_t p, float* dx, void* stream) {
+  if (!dy || !argmax || !dx || N < 1 || M < 1 || F < 1 || p < 1 || M % p)
+    return fail(CG_ERR_ARG, "maxpool_backward: bad arguments (M=%d p=%d)", M, p);
+  CG_HIP(cg::launch_maxpool_bwd(dy, argmax, N, M, F, p, dx, reinterpret_cast<hipStream_t>(stream)));
+  return ok();
+}
+
+int cg_avgpool_forward(const float* x, int32_t N, int32_t M, int32_t F, int32_t p, float* y,
+                       void* stream) {
+  if (!x || !y || N < 1 || M < 1 || F < 1 || p < 1 || M % p)
+    return fail(CG_ERR_ARG, "avgpool_forward: bad arguments (M=%d p=%d)", M, p);
+  CG_HIP(cg::launch_avgpool_fwd(x, N, M, F, p, y, reinterpret_cast<hipStream_t>(stream)));
+  return ok();
+}
+
+int cg_avgpool_backward(const float* dy, int32_t N, int32_t M, int32_t F, int32_t p, float* dx,
+                        void* stream) {
+  if (!dy || !dx || N < 1 || M < 1 || F < 1 || p < 1 || M % p)
+    return fail(CG_ERR_ARG, "avgpool_backward: bad arguments (M=%d p=%d)", M, p);
+  CG_HIP(cg::launch_avgpool_bwd(dy, N, M, F, p, dx, reinterpret_cast<hipStream_t>(stream)));
+  return ok();
+}
+
+int cg_adam_update(float* param, const float* grad, float* m, float* v, int64_t n, float lr,
+                   float beta1, float beta2, float eps, int32_t step, float grad_scale,
+                   void* stream) {
+  if (!param || !grad || !m || !v || n < 0 || step < 1)
+    return fail(CG_ERR_ARG, "adam_update: bad arguments");
+  if (n == 0) return ok();
+  CG_HIP(cg::launch_adam(param, grad, m, v, n, cg::adam_lr_t(lr, beta1, beta2, step), beta1, beta2, eps,
+                         grad_scale,
+                         reinterpret_cast<hipStream_t>(stream)));
+  return ok();
+}
+
+int cg_sgd_update(float* param, const float* grad, int64_t n, float lr, float grad_scale,
+                  void* stream) {
+  if (!param || !grad || n < 0) return fail(CG_ERR_ARG, "sgd_update: bad arguments");
+  if (n == 0) return ok();
+  CG_HIP(cg::launch_sgd(param, grad, n, lr, grad_scale, reinterpret_cast<hipStream_t>(stream)));
+  return ok();
+}
+
+int cg_rmsprop_update(float* param, const float* grad, float* ms, float* mom, int64_t n, float lr,
+                      float rho, float momentum, float eps, float grad_scale, void* stream) {
+  if (!param || !grad || !ms || !mom || n < 0 || !(eps > 0.f))
+    return fail(CG_ERR_ARG, "rmsprop_update: bad arguments");
+  if (n == 0) return ok();
+  CG_HIP(cg::launch_rmsprop(param, grad, ms, mom, n, lr, rho, momentum, eps, grad_scale,
+                            reinterpret_cast<hipStream_t>(stream)));
+  return ok();
+}
+
+}  // extern "C"

@@ -82,8 +82,8 @@ class GConvRNNModel(LSTMStackTrainer):
         self.b, self.db = self.carve((1,), "gconv_model/bias", init=b0)
         self._carved()
         self.loss_scale = 1.0 / self.T
-        self.xws = torch.empty(max(ops.seq_xent_workspace_bytes(self.T, self.N, self.M, H), 1),
-                               device=self.device, dtype=torch.uint8)
+        self.xws, _ = ops._workspace("cg_seq_xent_workspace_bytes", self.T, self.N, self.M, H,
+                                     device=self.device)
         self._no_labels = torch.zeros((self.T, self.N), device=self.device, dtype=torch.int32)
 
     # -- FlatTrainer's hooks -------------------------------------------------------

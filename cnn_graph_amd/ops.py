@@ -61,6 +61,67 @@ def _check_out(name, t, shape):
                          f"got {tuple(t.shape)}")
 
 
+def _ws_bytes(entry, *args, sizes=1):
+    """The ``sizes`` byte counts a cg_*_workspace_bytes entry reports for ``args``."""
+    out = [ctypes.c_size_t() for _ in range(sizes)]
+    _lib.call(entry, *args, *(ctypes.byref(o) for o in out))
+    return [o.value for o in out]
+
+
+def _workspace(entry, *args, device, sizes=1, pick=0):
+    """(uint8 tensor, nbytes): a fresh workspace of the size ``entry`` reports
+    (number ``pick`` of its ``sizes``), at least 1 byte.  Not cached: only the
+    plan's per-stream buffer (_plan_ws) is.  Shared package-wide: trainer.py and
+    gconv_rnn.py size their preallocated workspaces with it."""
+    nbytes = _ws_bytes(entry, *args, sizes=sizes)[pick]
+    return torch.empty(max(nbytes, 1), device=device, dtype=torch.uint8), nbytes
+
+
+def _out(name, given, shape, device, elems=None, accumulate=False):
+    """The caller's output tensor or a fresh fp32 one of ``shape``, checked by
+    _check_out against ``elems`` (default: shape).  accumulate: there must be a
+    given tensor to add into."""
+    if given is None:
+        if accumulate:
+            raise ValueError("accumulate=True needs an out tensor")
+        given = torch.empty(tuple(shape), device=device, dtype=torch.float32)
+    _check_out(name, given, elems if elems is not None else shape)
+    return given
+
+
+def _check_opt(name, t, n: int, aligned: bool):
+    """An optional input: None, or fp32 on the GPU, contiguous, n elements and --
+    where the kernel reads it as float4 -- 16-byte aligned."""
+    if t is None:
+        return
+    _check_dev(name, t)
+    if not t.is_contiguous() or t.numel() != n or (aligned and t.data_ptr() % 16):
+        raise ValueError(f"{name}: need a contiguous{' 16-byte aligned' if aligned else ''} tensor "
+                         f"of {n} floats, got {tuple(t.shape)}")
+
+
+def _check_planes(name, t, n: int, stride: int, per: int, aligned: bool):
+    """``t``'s storage holds n planes of ``per`` floats, ``stride`` floats apart,
+    from t's first element on; aligned: the kernel moves them as float4."""
+    avail = t.untyped_storage().nbytes() // 4 - t.storage_offset()
+    if n > 0 and (stride < per or avail < (n - 1) * stride + per):
+        raise ValueError(f"{name}: storage too small for {n} planes of {per} floats at this stride")
+    if aligned and (t.data_ptr() % 16 or (n > 0 and stride % 4)):
+        raise ValueError(f"{name}: needs a 16-byte aligned start and a stride that is a "
+                         "multiple of 4 floats (the kernel moves float4)")
+
+
+def _check_weight(name, W, rows: int, cols: int):
+    if tuple(W.shape) != (rows, cols) or not W.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous [{rows}, {cols}] tensor")
+
+
+def _supported(entry, *args) -> bool:
+    ok = ctypes.c_int32()
+    _lib.call(entry, *args, ctypes.byref(ok))
+    return bool(ok.value)
+
+
 ACTS = {"none": _lib.CG_ACT_NONE, "relu": _lib.CG_ACT_RELU}
 
 
@@ -98,12 +159,9 @@ def cheb_forward(plan: ChebPlan, x: torch.Tensor, W: torch.Tensor | None, K: int
     basis = y = None
     if need_basis:
         shape = (K, N * M, Fin) if layout == "planes" else (N * M, Fin * K)
-        basis = out_basis if out_basis is not None else torch.empty(shape, device=dev,
-                                                                    dtype=torch.float32)
-        _check_out("out_basis", basis, (N * M, Fin * K))
+        basis = _out("out_basis", out_basis, shape, dev, elems=(N * M, Fin * K))
     if W is not None:
-        y = out_y if out_y is not None else torch.empty((N, M, Fout), device=dev, dtype=torch.float32)
-        _check_out("out_y", y, (N * M * Fout,))
+        y = _out("out_y", out_y, (N, M, Fout), dev, elems=(N * M * Fout,))
     if residual is not None:
         _check_dev("residual", residual)
         residual = residual.contiguous()
@@ -172,13 +230,10 @@ def mse_loss(pred: torch.Tensor, labels: torch.Tensor, need_grad: bool = True):
     if pred.numel() != labels.numel():
         raise ValueError("pred and labels differ in size")
     n = pred.numel()
-    nb = ctypes.c_size_t()
-    _lib.call("cg_mse_loss_workspace_bytes", n, ctypes.byref(nb))
-    ws = torch.empty(max(nb.value, 1), device=pred.device, dtype=torch.uint8)
+    ws, nb = _workspace("cg_mse_loss_workspace_bytes", n, device=pred.device)
     loss = torch.empty((1,), device=pred.device, dtype=torch.float32)
     dpred = torch.empty_like(pred) if need_grad else None
-    _lib.call("cg_mse_loss", _p(pred), _p(labels), n, _p(loss), _p(dpred), _p(ws), nb.value,
-              _stream(pred))
+    _lib.call("cg_mse_loss", _p(pred), _p(labels), n, _p(loss), _p(dpred), _p(ws), nb, _stream(pred))
     return loss, dpred
 
 
@@ -462,16 +517,10 @@ def weight_grad(basis: torch.Tensor, dy: torch.Tensor, out: torch.Tensor | None 
     Fout = int(dy.shape[-1])
     if dy.numel() != R * Fout:
         raise ValueError(f"dy has {dy.numel()} elements, expected R*Fout = {R * Fout}")
-    if out is None:
-        if accumulate:
-            raise ValueError("accumulate=True needs an out tensor")
-        out = torch.empty((FinK, Fout), device=basis.device, dtype=torch.float32)
-    _check_out("out", out, (FinK, Fout))
-    nb = ctypes.c_size_t()
-    _lib.call("cg_weight_grad_workspace_bytes", R, FinK, Fout, ctypes.byref(nb))
-    ws = torch.empty(max(nb.value, 1), device=basis.device, dtype=torch.uint8)
+    out = _out("out", out, (FinK, Fout), basis.device, accumulate=accumulate)
+    ws, nb = _workspace("cg_weight_grad_workspace_bytes", R, FinK, Fout, device=basis.device)
     _lib.call("cg_weight_grad", R, FinK, Fout, _p(basis.contiguous()), _p(dy.contiguous()), _p(out),
-              int(accumulate), _p(ws), nb.value, _stream(basis))
+              int(accumulate), _p(ws), nb, _stream(basis))
     return out
 
 
@@ -486,19 +535,11 @@ def weight_grad_planes(planes: torch.Tensor, plane_stride: int, K: int, R: int, 
     Fout = int(dy.shape[-1])
     if dy.numel() != R * Fout or not dy.is_contiguous():
         raise ValueError(f"dy must be a contiguous tensor of R*Fout = {R * Fout} elements")
-    avail = planes.untyped_storage().nbytes() // 4 - planes.storage_offset()
-    if plane_stride < R * Fin or avail < (K - 1) * plane_stride + R * Fin:
-        raise ValueError("planes: storage too small for K planes at this stride")
-    if out is None:
-        if accumulate:
-            raise ValueError("accumulate=True needs an out tensor")
-        out = torch.empty((Fin * K, Fout), device=planes.device, dtype=torch.float32)
-    _check_out("out", out, (Fin * K, Fout))
-    nb = ctypes.c_size_t()
-    _lib.call("cg_weight_grad_workspace_bytes", R, Fin * K, Fout, ctypes.byref(nb))
-    ws = torch.empty(max(nb.value, 1), device=planes.device, dtype=torch.uint8)
+    _check_planes("planes", planes, K, plane_stride, R * Fin, aligned=False)
+    out = _out("out", out, (Fin * K, Fout), planes.device, accumulate=accumulate)
+    ws, nb = _workspace("cg_weight_grad_workspace_bytes", R, Fin * K, Fout, device=planes.device)
     _lib.call("cg_weight_grad_planes", int(R), Fin, int(K), Fout, _p(planes), int(plane_stride),
-              _p(dy), _p(out), int(accumulate), _p(ws), nb.value, _stream(planes))
+              _p(dy), _p(out), int(accumulate), _p(ws), nb, _stream(planes))
     return out
 
 
@@ -513,21 +554,17 @@ def lstm_weight_grads(h_planes: torch.Tensor, h_plane_stride: int, x_planes: tor
     H, Fin = int(h_planes.shape[-1]), int(x_planes.shape[-1])
     if dpre.numel() != R * 4 * H or not dpre.is_contiguous():
         raise ValueError(f"dpre must be a contiguous tensor of R*4H = {R * 4 * H} elements")
-    for name, t, st, w in (("h_planes", h_planes, h_plane_stride, H),
-                           ("x_planes", x_planes, x_plane_stride, Fin)):
-        avail = t.untyped_storage().nbytes() // 4 - t.storage_offset()
-        if st < R * w or avail < (K - 1) * st + R * w:
-            raise ValueError(f"{name}: storage too small for K planes at this stride")
+    _check_planes("h_planes", h_planes, K, h_plane_stride, R * H, aligned=False)
+    _check_planes("x_planes", x_planes, K, x_plane_stride, R * Fin, aligned=False)
     f32 = dict(device=dpre.device, dtype=torch.float32)
     dWh = torch.empty((H * K, 4 * H), **f32)
     dWx = torch.empty((Fin * K, 4 * H), **f32)
     db = torch.empty((4 * H,), **f32)
-    nb = ctypes.c_size_t()
-    _lib.call("cg_lstm_weight_grads_workspace_bytes", int(R), H, Fin, int(K), ctypes.byref(nb))
-    ws = torch.empty(max(nb.value, 1), device=dpre.device, dtype=torch.uint8)
+    ws, nb = _workspace("cg_lstm_weight_grads_workspace_bytes", int(R), H, Fin, int(K),
+                        device=dpre.device)
     _lib.call("cg_lstm_weight_grads", int(R), H, Fin, int(K), _p(h_planes), int(h_plane_stride),
               _p(x_planes), int(x_plane_stride), _p(dpre), _p(dWh), _p(dWx), _p(db), _p(ws),
-              nb.value, _stream(dpre))
+              nb, _stream(dpre))
     return dWh, dWx, db
 
 
@@ -536,20 +573,21 @@ def bias_grad(dy: torch.Tensor, out: torch.Tensor | None = None, accumulate: boo
     _check_dev("dy", dy)
     C = int(dy.shape[-1])
     R = dy.numel() // C
-    if out is None:
-        if accumulate:
-            raise ValueError("accumulate=True needs an out tensor")
-        out = torch.empty((C,), device=dy.device, dtype=torch.float32)
-    _check_out("out", out, (C,))
-    nb = ctypes.c_size_t()
-    _lib.call("cg_bias_grad_workspace_bytes", R, C, ctypes.byref(nb))
-    ws = torch.empty(max(nb.value, 1), device=dy.device, dtype=torch.uint8)
-    _lib.call("cg_bias_grad", R, C, _p(dy.contiguous()), _p(out), int(accumulate), _p(ws), nb.value,
+    out = _out("out", out, (C,), dy.device, accumulate=accumulate)
+    ws, nb = _workspace("cg_bias_grad_workspace_bytes", R, C, device=dy.device)
+    _lib.call("cg_bias_grad", R, C, _p(dy.contiguous()), _p(out), int(accumulate), _p(ws), nb,
               _stream(dy))
     return out
 
 
 LSTM_GATES = {"reference": 0, "standard": 1}
+
+
+def _cell_outs(out_c, out_h, out_act, lead, R: int, H: int, dev):
+    """(c', h', act) of one cell step: the caller's or fresh [*lead, H] / [*lead, 4H]."""
+    return (_out("c_out", out_c, lead + (H,), dev, elems=(R, H)),
+            _out("h_out", out_h, lead + (H,), dev, elems=(R, H)),
+            _out("act", out_act, lead + (4 * H,), dev, elems=(R, 4 * H)))
 
 
 def lstm_cell_forward(gx, gh, bias, c, H: int, gates="reference", out_c=None, out_h=None,
@@ -561,18 +599,9 @@ def lstm_cell_forward(gx, gh, bias, c, H: int, gates="reference", out_c=None, ou
     R = gx.numel() // (4 * H)
     lead = tuple(gx.shape[:-1])
     dev = gx.device
-    for name, t, n in (("gh", gh, 4 * H), ("bias", bias, 4 * H), ("c", c, H)):
-        if t is not None:
-            _check_dev(name, t)
-            if not t.is_contiguous() or t.numel() != (n if name == "bias" else R * n):
-                raise ValueError(f"{name}: bad shape {tuple(t.shape)}")
-    c_out = out_c if out_c is not None else torch.empty(lead + (H,), device=dev, dtype=torch.float32)
-    h_out = out_h if out_h is not None else torch.empty(lead + (H,), device=dev, dtype=torch.float32)
-    act = out_act if out_act is not None else torch.empty(lead + (4 * H,), device=dev,
-                                                          dtype=torch.float32)
-    _check_out("c_out", c_out, (R, H))
-    _check_out("h_out", h_out, (R, H))
-    _check_out("act", act, (R, 4 * H))
+    for name, t, n in (("gh", gh, R * 4 * H), ("bias", bias, 4 * H), ("c", c, R * H)):
+        _check_opt(name, t, n, aligned=False)
+    c_out, h_out, act = _cell_outs(out_c, out_h, out_act, lead, R, H, dev)
     _lib.call("cg_lstm_cell_forward", R, H, LSTM_GATES[gates], _p(gx.contiguous()), _p(gh), _p(bias),
               _p(c), _p(c_out), _p(h_out), _p(act), _stream(gx))
     return c_out, h_out, act
@@ -580,9 +609,7 @@ def lstm_cell_forward(gx, gh, bias, c, H: int, gates="reference", out_c=None, ou
 
 def lstm_hconv_supported(plan: ChebPlan, H: int, K: int) -> bool:
     """Whether cg_lstm_hconv_step serves this graph / hidden size / order."""
-    ok = ctypes.c_int32()
-    _lib.call("cg_lstm_hconv_supported", plan.handle, int(H), int(K), ctypes.byref(ok))
-    return bool(ok.value)
+    return _supported("cg_lstm_hconv_supported", plan.handle, int(H), int(K))
 
 
 def lstm_hconv_step(plan: ChebPlan, h_prev, c_prev, gx, Wh, bias, K: int, gates="reference",
@@ -597,29 +624,13 @@ def lstm_hconv_step(plan: ChebPlan, h_prev, c_prev, gx, Wh, bias, K: int, gates=
     N, M, H = (int(v) for v in h_prev.shape)
     R = N * M
     dev = h_prev.device
-    for name, t, n in (("gx", gx, 4 * H), ("c_prev", c_prev, H), ("bias", bias, 4 * H)):
-        if t is not None:
-            _check_dev(name, t)
-            if not t.is_contiguous() or t.numel() != (n if name == "bias" else R * n):
-                raise ValueError(f"{name}: bad shape {tuple(t.shape)}")
-    if tuple(Wh.shape) != (K * H, 4 * H) or not Wh.is_contiguous():
-        raise ValueError(f"Wh must be a contiguous [{K * H}, {4 * H}] tensor")
-    c_out = out_c if out_c is not None else torch.empty((N, M, H), device=dev, dtype=torch.float32)
-    h_out = out_h if out_h is not None else torch.empty((N, M, H), device=dev, dtype=torch.float32)
-    act = out_act if out_act is not None else torch.empty((N, M, 4 * H), device=dev,
-                                                          dtype=torch.float32)
-    _check_out("c_out", c_out, (R, H))
-    _check_out("h_out", h_out, (R, H))
-    _check_out("act", act, (R, 4 * H))
+    for name, t, n in (("gx", gx, R * 4 * H), ("c_prev", c_prev, R * H), ("bias", bias, 4 * H)):
+        _check_opt(name, t, n, aligned=False)
+    _check_weight("Wh", Wh, K * H, 4 * H)
+    c_out, h_out, act = _cell_outs(out_c, out_h, out_act, (N, M), R, H, dev)
     if planes is not None:
         _check_dev("planes", planes)
-        need = (K - 2) * plane_stride + R * H if K > 1 else 0
-        avail = planes.untyped_storage().nbytes() // 4 - planes.storage_offset()
-        if K > 1 and (plane_stride < R * H or avail < need):
-            raise ValueError("planes: storage too small for the K-1 planes at this stride")
-        if planes.data_ptr() % 16 or (K > 1 and plane_stride % 4):
-            raise ValueError("planes: needs a 16-byte aligned start and a stride that is a "
-                             "multiple of 4 floats (the kernel stores float4)")
+        _check_planes("planes", planes, K - 1, plane_stride, R * H, aligned=True)
     if h_prev.data_ptr() % 16:
         h_prev = h_prev.clone()  # float4 loads: a view at an odd offset is copied
     _lib.call("cg_lstm_hconv_step", plan.handle, N, H, int(K), LSTM_GATES[gates], _p(h_prev),
@@ -636,13 +647,8 @@ def lstm_cell_backward(dh, dh_rec, dc, act, c, c_out, H: int, gates="reference",
     R = act.numel() // (4 * H)
     dev = act.device
     for name, t in (("dh", dh), ("dh_rec", dh_rec), ("dc", dc), ("c", c)):
-        if t is not None:
-            _check_dev(name, t)
-            if not t.is_contiguous() or t.numel() != R * H:
-                raise ValueError(f"{name}: bad shape {tuple(t.shape)}")
-    dpre = out_dpre if out_dpre is not None else torch.empty(tuple(act.shape), device=dev,
-                                                             dtype=torch.float32)
-    _check_out("dpre", dpre, (R, 4 * H))
+        _check_opt(name, t, R * H, aligned=False)
+    dpre = _out("dpre", out_dpre, act.shape, dev, elems=(R, 4 * H))
     dc_prev = torch.empty(tuple(c_out.shape), device=dev, dtype=torch.float32) if need_dc_prev else None
     _lib.call("cg_lstm_cell_backward", R, H, LSTM_GATES[gates], _p(dh), _p(dh_rec), _p(dc), _p(act),
               _p(c), _p(c_out), _p(dpre), _p(dc_prev), _stream(act))
@@ -652,9 +658,7 @@ def lstm_cell_backward(dh, dh_rec, dc, act, c, c_out, H: int, gates="reference",
 def lstm_seq_supported(plan: ChebPlan, H: int, K: int) -> bool:
     """Whether the one-launch layer forward (cg_lstm_seq_forward) and the
     one-launch BPTT step (cg_lstm_bwd_step) serve this graph / H / K."""
-    ok = ctypes.c_int32()
-    _lib.call("cg_lstm_seq_supported", plan.handle, int(H), int(K), ctypes.byref(ok))
-    return bool(ok.value)
+    return _supported("cg_lstm_seq_supported", plan.handle, int(H), int(K))
 
 
 def lstm_seq_fault(plan: ChebPlan, wait: bool = True) -> bool | None:
@@ -676,30 +680,20 @@ def _lstm_seq_prepare(plan: ChebPlan, dev, T: int, N: int, M: int, H: int, K: in
     Returns (hs, cs, planes, plane_stride, workspace)."""
     R = T * N * M
     for name, t, n in (("bias", bias, 4 * H), ("h0", h0, N * M * H), ("c0", c0, N * M * H)):
-        if t is not None:
-            _check_dev(name, t)
-            if not t.is_contiguous() or t.numel() != n or t.data_ptr() % 16:
-                raise ValueError(f"{name}: need a contiguous 16-byte aligned tensor of {n} floats")
-    f32 = dict(device=dev, dtype=torch.float32)
-    hs = out_hs if out_hs is not None else torch.empty((T, N, M, H), **f32)
-    cs = out_cs if out_cs is not None else torch.empty((T, N, M, H), **f32)
-    _check_out("hs", hs, (R, H))
-    _check_out("cs", cs, (R, H))
+        _check_opt(name, t, n, aligned=True)
+    hs = _out("hs", out_hs, (T, N, M, H), dev, elems=(R, H))
+    cs = _out("cs", out_cs, (T, N, M, H), dev, elems=(R, H))
     if out_act is not None:
         _check_out("act", out_act, (R, 4 * H))
     if planes is None and K > 1:  # the kernel hands Chebyshev orders through them
-        planes = torch.empty((K - 1, R, H), **f32)
+        planes = torch.empty((K - 1, R, H), device=dev, dtype=torch.float32)
         plane_stride = R * H
     if planes is not None:
         _check_dev("planes", planes)
-        need = (K - 2) * plane_stride + R * H if K > 1 else 0
-        avail = planes.untyped_storage().nbytes() // 4 - planes.storage_offset()
-        if K > 1 and (plane_stride < R * H or avail < need or planes.data_ptr() % 16
-                      or plane_stride % 4):
-            raise ValueError("planes: storage too small / misaligned for the K-1 planes")
-    nb = ctypes.c_size_t()
-    _lib.call("cg_lstm_seq_workspace_bytes", plan.handle, int(N), ctypes.byref(nb))
-    return hs, cs, planes, plane_stride, torch.empty(int(nb.value), device=dev, dtype=torch.uint8)
+        if K > 1:  # (K = 1: no plane is written; the C entry judges the pointer)
+            _check_planes("planes", planes, K - 1, plane_stride, R * H, aligned=True)
+    ws, _ = _workspace("cg_lstm_seq_workspace_bytes", plan.handle, int(N), device=dev)
+    return hs, cs, planes, plane_stride, ws
 
 
 def lstm_seq_forward(plan: ChebPlan, gx, Wh, bias, K: int, T: int, N: int, gates="reference",
@@ -720,8 +714,7 @@ def lstm_seq_forward(plan: ChebPlan, gx, Wh, bias, K: int, T: int, N: int, gates
     R = T * N * M
     if not gx.is_contiguous() or gx.numel() != R * 4 * H:
         raise ValueError(f"gx must be a contiguous [{T}, {N}, {M}, {4 * H}] tensor")
-    if tuple(Wh.shape) != (K * H, 4 * H) or not Wh.is_contiguous():
-        raise ValueError(f"Wh must be a contiguous [{K * H}, {4 * H}] tensor")
+    _check_weight("Wh", Wh, K * H, 4 * H)
     hs, cs, planes, plane_stride, ws = _lstm_seq_prepare(plan, gx.device, T, N, M, H, K, bias, h0,
                                                          c0, out_hs, out_cs, out_act, planes,
                                                          plane_stride)
@@ -736,9 +729,7 @@ def lstm_seq_forward(plan: ChebPlan, gx, Wh, bias, K: int, T: int, N: int, gates
 
 def lstm_seq_x_supported(plan: ChebPlan, Fin: int, H: int, K: int) -> bool:
     """Whether cg_lstm_seq_forward_x (the x-conv fused in) serves feat_in = Fin."""
-    ok = ctypes.c_int32()
-    _lib.call("cg_lstm_seq_x_supported", plan.handle, int(Fin), int(H), int(K), ctypes.byref(ok))
-    return bool(ok.value)
+    return _supported("cg_lstm_seq_x_supported", plan.handle, int(Fin), int(H), int(K))
 
 
 def lstm_seq_forward_x(plan: ChebPlan, xs, Wx, Wh, bias, K: int, gates="reference", h0=None,
@@ -753,16 +744,12 @@ def lstm_seq_forward_x(plan: ChebPlan, xs, Wx, Wh, bias, K: int, gates="referenc
     H = int(Wh.shape[1]) // 4
     R = T * N * M
     dev = xs.device
-    if tuple(Wx.shape) != (K * F, 4 * H) or not Wx.is_contiguous():
-        raise ValueError(f"Wx must be a contiguous [{K * F}, {4 * H}] tensor")
-    if tuple(Wh.shape) != (K * H, 4 * H) or not Wh.is_contiguous():
-        raise ValueError(f"Wh must be a contiguous [{K * H}, {4 * H}] tensor")
+    _check_weight("Wx", Wx, K * F, 4 * H)
+    _check_weight("Wh", Wh, K * H, 4 * H)
     hs, cs, planes, plane_stride, ws = _lstm_seq_prepare(plan, dev, T, N, M, H, K, bias, h0, c0,
                                                          out_hs, out_cs, out_act, planes,
                                                          plane_stride)
-    if xplanes is None:
-        xplanes = torch.empty((K, R, F), device=dev, dtype=torch.float32)
-    _check_out("xplanes", xplanes, (K * R * F,))
+    xplanes = _out("xplanes", xplanes, (K, R, F), dev, elems=(K * R * F,))
     s = _stream(xs)
     _lib.call("cg_lstm_seq_forward_x", plan.handle, T, N, F, int(H), int(K), LSTM_GATES[gates],
               _p(xs), _p(Wx), _p(xplanes), R * F, _p(Wh), _p(bias), _p(h0), _p(c0), _p(hs), _p(cs),
@@ -791,23 +778,13 @@ def lstm_bwd_step(plan: ChebPlan, dh, dh_rec, dc, act, c_prev, c_out, Wh, K: int
     dev = act.device
     for name, t in (("dh", dh), ("dh_rec", dh_rec), ("dc", dc), ("c_prev", c_prev),
                     ("c_out", c_out)):
-        if t is not None:
-            _check_dev(name, t)
-            if not t.is_contiguous() or t.numel() != R * H or t.data_ptr() % 16:
-                raise ValueError(f"{name}: bad shape / alignment {tuple(t.shape)}")
+        _check_opt(name, t, R * H, aligned=True)
     if not act.is_contiguous() or act.data_ptr() % 16:
         raise ValueError("act: need a contiguous 16-byte aligned tensor")
-    if tuple(Wh.shape) != (K * H, 4 * H) or not Wh.is_contiguous():
-        raise ValueError(f"Wh must be a contiguous [{K * H}, {4 * H}] tensor")
-    f32 = dict(device=dev, dtype=torch.float32)
-    dpre = out_dpre if out_dpre is not None else \
-        torch.empty(tuple(c_out.shape[:-1]) + (4 * H,), **f32)
-    _check_out("dpre", dpre, (R, 4 * H))
-    dc_prev = torch.empty(tuple(c_out.shape), **f32) if need_dc_prev else None
-    dh_prev = None
-    if need_dh_prev:
-        dh_prev = out_dh_prev if out_dh_prev is not None else torch.empty(tuple(c_out.shape), **f32)
-        _check_out("dh_prev", dh_prev, (R, H))
+    _check_weight("Wh", Wh, K * H, 4 * H)
+    dpre = _out("dpre", out_dpre, tuple(c_out.shape[:-1]) + (4 * H,), dev, elems=(R, 4 * H))
+    dc_prev = torch.empty(tuple(c_out.shape), device=dev, dtype=torch.float32) if need_dc_prev else None
+    dh_prev = _out("dh_prev", out_dh_prev, c_out.shape, dev, elems=(R, H)) if need_dh_prev else None
     _lib.call("cg_lstm_bwd_step", plan.handle, int(N), int(H), int(K), LSTM_GATES[gates], _p(dh),
               _p(dh_rec), _p(dc), _p(act), int(bool(act_unit_major)), _p(c_prev), _p(c_out), _p(Wh),
               _p(dpre), _p(dc_prev),
@@ -895,9 +872,7 @@ def seq_xent_labels(labels, M: int, device) -> torch.Tensor:
 
 
 def seq_xent_workspace_bytes(T: int, N: int, M: int, H: int) -> int:
-    nb = ctypes.c_size_t()
-    _lib.call("cg_seq_xent_workspace_bytes", int(T), int(N), int(M), int(H), ctypes.byref(nb))
-    return nb.value
+    return _ws_bytes("cg_seq_xent_workspace_bytes", int(T), int(N), int(M), int(H))[0]
 
 
 def seq_xent_call(hs, w, b, labels, keep: float = 1.0, seed: int = 0, loss_scale: float = 1.0,
@@ -919,20 +894,18 @@ def seq_xent_call(hs, w, b, labels, keep: float = 1.0, seed: int = 0, loss_scale
         raise ValueError(f"need w [{H}], b [1] and labels [{T}, {N}]")
     hs, w, labels = hs.contiguous(), w.contiguous(), labels.contiguous()
     f32 = dict(device=hs.device, dtype=torch.float32)
-    nb = seq_xent_workspace_bytes(T, N, M, H)
     if ws is None:
-        ws = torch.empty(nb, device=hs.device, dtype=torch.uint8)
+        ws, _ = _workspace("cg_seq_xent_workspace_bytes", T, N, M, H, device=hs.device)
+    else:
+        seq_xent_workspace_bytes(T, N, M, H)  # (the query also judges the shape)
     loss = torch.empty((1,), **f32)
     logits = torch.empty((N, M, T), **f32) if want_logits else None
     ce = torch.empty((T, N), **f32) if want_ce else None
     dhs = dw = db = None
     if need_grad:
-        dhs = out_dhs if out_dhs is not None else torch.empty_like(hs)
-        dw = out_dw if out_dw is not None else torch.empty((H,), **f32)
-        db = out_db if out_db is not None else torch.empty((1,), **f32)
-        _check_out("out_dhs", dhs, hs.shape)
-        _check_out("out_dw", dw, (H,))
-        _check_out("out_db", db, (1,))
+        dhs = _out("out_dhs", out_dhs, hs.shape, hs.device)
+        dw = _out("out_dw", out_dw, (H,), hs.device)
+        db = _out("out_db", out_db, (1,), hs.device)
     _lib.call("cg_seq_xent_head", _p(hs), _p(w), _p(b), _p(labels), T, N, M, H, float(keep),
               int(seed) & ((1 << 64) - 1), float(loss_scale), _p(logits), _p(ce), _p(loss), _p(dhs),
               _p(dw), _p(db), _p(ws), ws.numel(), _stream(hs))
@@ -1049,10 +1022,7 @@ class _BiasAct(torch.autograd.Function):
         nb = 0
         if ctx.has_bias and ctx.needs_input_grad[1]:
             db = torch.empty(ctx.bshape, device=dy.device, dtype=torch.float32)
-            b = ctypes.c_size_t()
-            _lib.call("cg_bias_act_workspace_bytes", n, ctx.blen, ctypes.byref(b))
-            nb = b.value
-            ws = torch.empty(max(nb, 1), device=dy.device, dtype=torch.uint8)
+            ws, nb = _workspace("cg_bias_act_workspace_bytes", n, ctx.blen, device=dy.device)
         _lib.call("cg_bias_act_backward", n, ctx.blen, _p(dy), _p(y), BIAS_ACTS[ctx.act], _p(dz), _p(db),
                   0, _p(ws), nb, _stream(dy))
         return dz, db, None
@@ -1075,9 +1045,7 @@ def gemm(a: torch.Tensor, b: torch.Tensor, trans_a: bool = False, trans_b: bool 
     Kb, N = (b.shape[1], b.shape[0]) if trans_b else (b.shape[0], b.shape[1])
     if K != Kb:
         raise ValueError(f"gemm: inner dimensions differ ({K} vs {Kb})")
-    if out is None:
-        out = torch.empty((M, N), device=a.device, dtype=torch.float32)
-    _check_out("out", out, (M, N))
+    out = _out("out", out, (M, N), a.device)
     _lib.call("cg_gemm_f32", int(trans_a), int(trans_b), M, N, K, _p(a), a.shape[1], _p(b), b.shape[1],
               _p(out), N, _stream(a))
     return out
@@ -1114,15 +1082,15 @@ class _Fourier(torch.autograd.Function):
             raise ValueError(f"fourier: need W [M, Fout, Fin] = [{M}, *, {Fin}] and U [{M}, {M}], "
                              f"got {tuple(W.shape)} and {tuple(U.shape)}")
         Fout = int(W.shape[1])
-        fb, bb = ctypes.c_size_t(), ctypes.c_size_t()
-        _lib.call("cg_fourier_workspace_bytes", N, M, Fin, Fout, ctypes.byref(fb), ctypes.byref(bb))
+        # one query for both sizes: the backward's is kept on ctx, not asked for again
+        fb, bb = _ws_bytes("cg_fourier_workspace_bytes", N, M, Fin, Fout, sizes=2)
         xhat = torch.empty((N, Fin, M), device=x.device, dtype=torch.float32)
         y = torch.empty((N, M, Fout), device=x.device, dtype=torch.float32)
-        ws = torch.empty(max(fb.value, 1), device=x.device, dtype=torch.uint8)
+        ws = torch.empty(max(fb, 1), device=x.device, dtype=torch.uint8)
         _lib.call("cg_fourier_forward", N, M, Fin, Fout, _p(U), _p(W), _p(x), _p(xhat), _p(y), _p(ws),
-                  fb.value, _stream(x))
+                  fb, _stream(x))
         ctx.save_for_backward(xhat, W, U)
-        ctx.shape, ctx.bwd_bytes = (N, M, Fin, Fout), bb.value
+        ctx.shape, ctx.bwd_bytes = (N, M, Fin, Fout), bb
         return y
 
     @staticmethod
@@ -1156,10 +1124,8 @@ def gft_prepare(U: torch.Tensor) -> torch.Tensor:
     M = int(U.shape[0])
     if tuple(U.shape) != (M, M):
         raise ValueError(f"U must be square, got {tuple(U.shape)}")
-    nb = ctypes.c_size_t()
-    _lib.call("cg_gft_workspace_bytes", M, ctypes.byref(nb))
-    basis = torch.empty(nb.value, device=U.device, dtype=torch.uint8)
-    _lib.call("cg_gft_prepare", M, _p(U), _p(basis), nb.value, _stream(U))
+    basis, nb = _workspace("cg_gft_workspace_bytes", M, device=U.device)
+    _lib.call("cg_gft_prepare", M, _p(U), _p(basis), nb, _stream(U))
     return basis
 
 
@@ -1170,9 +1136,7 @@ def gft(basis: torch.Tensor, x: torch.Tensor, inverse: bool = False, out: torch.
     x = x.contiguous()
     M, C = int(x.shape[-2]), int(x.shape[-1])
     N = x.numel() // (M * C)
-    if out is None:
-        out = torch.empty(tuple(x.shape), device=x.device, dtype=torch.float32)
-    _check_out("out", out, (N, M, C))
+    out = _out("out", out, x.shape, x.device, elems=(N, M, C))
     _lib.call("cg_gft", int(bool(inverse)), N, M, C, _p(basis), basis.numel(), _p(x), _p(out),
               _stream(x))
     return out
@@ -1222,10 +1186,7 @@ def fourier_mix(form: str, W=None, x=None, g=None, add=None, out=None):
 # -- residual block with the Fourier filter (lib/graph_conv.py:83-111 in :234-262) ------
 def fres_workspace_bytes(N: int, M: int, Fin: int, Fout: int):
     """(forward, backward) workspace bytes of cg_fres_forward / cg_fres_backward."""
-    fb, bb = ctypes.c_size_t(), ctypes.c_size_t()
-    _lib.call("cg_fres_workspace_bytes", int(N), int(M), int(Fin), int(Fout), ctypes.byref(fb),
-              ctypes.byref(bb))
-    return fb.value, bb.value
+    return tuple(_ws_bytes("cg_fres_workspace_bytes", int(N), int(M), int(Fin), int(Fout), sizes=2))
 
 
 def _check_keep(keep_prob):
@@ -1252,18 +1213,15 @@ def fres_forward(basis, W, x, residual=None, act: str = "none", out_xhat=None, o
     if W.dim() != 3 or tuple(W.shape[::2]) != (M, Fin):
         raise ValueError(f"W must be [M, Fout, Fin] = [{M}, *, {Fin}], got {tuple(W.shape)}")
     Fout = int(W.shape[1])
-    f32 = dict(device=x.device, dtype=torch.float32)
     if residual is not None:
         _check_dev("residual", residual)
         residual = residual.contiguous()
         if residual.numel() != N * M * Fout:
             raise ValueError(f"residual must be [N, M, Fout] = [{N}, {M}, {Fout}]")
-    xhat = out_xhat if out_xhat is not None else torch.empty((N, M, Fin), **f32)
-    y = out_y if out_y is not None else torch.empty((N, M, Fout), **f32)
-    _check_out("xhat", xhat, (N, M, Fin))
-    _check_out("y", y, (N, M, Fout))
+    xhat = _out("xhat", out_xhat, (N, M, Fin), x.device)
+    y = _out("y", out_y, (N, M, Fout), x.device)
     if ws is None:
-        ws = torch.empty(fres_workspace_bytes(N, M, Fin, Fout)[0], device=x.device, dtype=torch.uint8)
+        ws, _ = _workspace("cg_fres_workspace_bytes", N, M, Fin, Fout, device=x.device, sizes=2)
     head = (N, M, Fin, Fout, _p(basis), basis.numel(), _p(W), _p(x))
     tail = (_p(residual), ACTS[act], _p(xhat), _p(y), _p(ws), ws.numel(), _stream(x))
     if keep_prob == 1.0:
@@ -1306,14 +1264,11 @@ def fres_backward(basis, W, xhat, dy, y=None, act: str = "none", need_dz: bool =
         dx = None
     if dx is not None:
         _check_out("dx", dx, (N, M, Fin))
-    dz = None
-    if need_dz:
-        dz = out_dz if out_dz is not None else torch.empty((N, M, Fout), **f32)
-        _check_out("dz", dz, (N, M, Fout))
-    dW = out_dW if out_dW is not None else torch.empty((M, Fout, Fin), **f32)
-    _check_out("dW", dW, (M, Fout, Fin))
+    dz = _out("dz", out_dz, (N, M, Fout), dy.device) if need_dz else None
+    dW = _out("dW", out_dW, (M, Fout, Fin), dy.device)
     if ws is None:
-        ws = torch.empty(fres_workspace_bytes(N, M, Fin, Fout)[1], device=dy.device, dtype=torch.uint8)
+        ws, _ = _workspace("cg_fres_workspace_bytes", N, M, Fin, Fout, device=dy.device, sizes=2,
+                           pick=1)
     head = (N, M, Fin, Fout, _p(basis), basis.numel(), _p(W), _p(xhat), _p(dy),
             _p(y) if act == "relu" else None, ACTS[act])
     tail = (_p(dW), _p(ws), ws.numel(), _stream(dy))
@@ -1369,9 +1324,7 @@ def fourier_conv_act(x, W, basis, residual=None, act: str = "none"):
 
 def flstm_supported(M: int, H: int, Fin: int) -> bool:
     """Whether cg_flstm_step serves this hidden size (H a multiple of 8)."""
-    ok = ctypes.c_int32()
-    _lib.call("cg_flstm_supported", int(M), int(H), int(Fin), ctypes.byref(ok))
-    return bool(ok.value)
+    return _supported("cg_flstm_supported", int(M), int(H), int(Fin))
 
 
 def flstm_step(basis, h_prev, c_prev, ghat_x, Wh, bias, gates="reference", out_c=None, out_h=None,
@@ -1387,25 +1340,12 @@ def flstm_step(basis, h_prev, c_prev, ghat_x, Wh, bias, gates="reference", out_c
     dev = ghat_x.device
     for name, t, n in (("h_prev", h_prev, R * H), ("c_prev", c_prev, R * H), ("bias", bias, 4 * H),
                        ("Wh", Wh, M * 4 * H * H), ("ghat_x", ghat_x, R * 4 * H)):
-        if t is not None:
-            _check_dev(name, t)
-            if not t.is_contiguous() or t.numel() != n:
-                raise ValueError(f"{name}: bad shape {tuple(t.shape)}")
-    f32 = dict(device=dev, dtype=torch.float32)
-    c_out = out_c if out_c is not None else torch.empty((N, M, H), **f32)
-    h_out = out_h if out_h is not None else torch.empty((N, M, H), **f32)
-    act = out_act if out_act is not None else torch.empty((N, M, 4 * H), **f32)
-    _check_out("c_out", c_out, (R, H))
-    _check_out("h_out", h_out, (R, H))
-    _check_out("act", act, (R, 4 * H))
+        _check_opt(name, t, n, aligned=False)
+    c_out, h_out, act = _cell_outs(out_c, out_h, out_act, (N, M), R, H, dev)
     hhat, ws, nbytes = None, None, 0
     if h_prev is not None:
-        hhat = out_hhat if out_hhat is not None else torch.empty((N, M, H), **f32)
-        _check_out("hhat", hhat, (R, H))
-        nb = ctypes.c_size_t()
-        _lib.call("cg_flstm_workspace_bytes", N, M, H, ctypes.byref(nb))
-        nbytes = nb.value
-        ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+        hhat = _out("hhat", out_hhat, (N, M, H), dev, elems=(R, H))
+        ws, nbytes = _workspace("cg_flstm_workspace_bytes", N, M, H, device=dev)
     _lib.call("cg_flstm_step", N, M, H, LSTM_GATES[gates], _p(basis), basis.numel(), _p(h_prev),
               _p(c_prev), _p(ghat_x), _p(Wh), _p(bias), _p(c_out), _p(h_out), _p(act), _p(hhat),
               _p(ws), nbytes, _stream(ghat_x))

@@ -28,6 +28,7 @@ import torch
 
 from . import _lib
 from . import evaluate as _ev
+from . import ops
 
 OPTIMIZERS = ("adam", "sgd", "rmsprop")
 
@@ -54,10 +55,8 @@ class FlatTrainer:
         # {biased, average, local_step} of ExponentialMovingAverage(0.9) of the loss
         self.ema = torch.zeros((3,), **f32)
         self.dout = torch.empty(tuple(out_shape), **f32)
-        nb = ctypes.c_size_t()
-        _lib.call("cg_mse_loss_workspace_bytes", math.prod(out_shape), ctypes.byref(nb))
-        self.mws = torch.empty(max(nb.value, 1), device=self.device, dtype=torch.uint8)
-        self.mws_n = nb.value
+        self.mws, self.mws_n = ops._workspace("cg_mse_loss_workspace_bytes", math.prod(out_shape),
+                                              device=self.device)
         self.step_count = 0
         # names / tensors / gradient views in carving order; ``params``: the
         # autograd-owned ones (torch.nn.Parameter, .grad = the bucket view)
