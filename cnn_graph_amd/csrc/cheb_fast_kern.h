@@ -49,6 +49,7 @@
 #include <type_traits>
 
 #include "cg_internal.h"
+#include "launch.h"
 #include "split_bf16.h"
 
 namespace cg {
@@ -1004,26 +1005,14 @@ __global__ __launch_bounds__(kT) void cheb_bwd_fast(FastBwdArgs A) {
   CG_TS(A.ts, 5);
 }
 
-template <typename Kern>
-hipError_t allow_big_lds(Kern k) {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-}
-
 template <int FV, int NT, bool OB>
 hipError_t launch_fwd_fast_t(size_t lds, int N, const FastFwdArgs& a, hipStream_t s) {
-  static hipError_t attr = allow_big_lds(&cheb_fwd_fast<FV, NT, OB>);
-  if (attr != hipSuccess) return attr;
-  hipLaunchKernelGGL((cheb_fwd_fast<FV, NT, OB>), dim3(N), dim3(kT), lds, s, a);
-  return hipGetLastError();
+  return launch_big_lds(&cheb_fwd_fast<FV, NT, OB>, dim3(N), dim3(kT), lds, s, a);
 }
 
 template <int FV, int DW>
 hipError_t launch_bwd_fast_t(size_t lds, int N, const FastBwdArgs& a, hipStream_t s) {
-  static hipError_t attr = allow_big_lds(&cheb_bwd_fast<FV, DW>);
-  if (attr != hipSuccess) return attr;
-  hipLaunchKernelGGL((cheb_bwd_fast<FV, DW>), dim3(N), dim3(kT), lds, s, a);
-  return hipGetLastError();
+  return launch_big_lds(&cheb_bwd_fast<FV, DW>, dim3(N), dim3(kT), lds, s, a);
 }
 
 }  // namespace fastk

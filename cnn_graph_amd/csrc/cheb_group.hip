@@ -32,6 +32,7 @@
 // on one XCD (blocks b, b + 8, .. under round-robin placement) so their 32-byte
 // slices of each basis row merge in one L2.
 #include "cg_internal.h"
+#include "launch.h"
 #include "lds_spmm.h"
 
 namespace cg {
@@ -209,13 +210,13 @@ __global__ __launch_bounds__(kGT) void k_grp_fwd(GrpFwdArgs A) {
 // The same forward for 16-channel groups (Fin % 16 == 0): half the workgroups
 // of the 8-channel kernel, so config R's 100 samples x 2 groups fit the 256
 // CUs in ONE round (8-channel groups: 416 workgroups = two rounds, the second
-// 62 % full); measured 178 vs 192 us per call (profiles/r03_grp): a workgroup
-// with twice the channels takes nearly twice as long, the chip is busy either way.  ONE [M][16] slot: a step gathers T_k from it, each lane keeps
-// T_{k-1} of its own rows in registers, a barrier, the lane swaps its rows'
-// T_k out for T_{k+1}, a barrier.  SpMM lanes: (row lane / 4 of a 16-row half
-// tile, channels 4 (lane % 4) ..); MFMA lanes: (row j, channels 8hh .. 8hh+7).
-// Fout <= 32 only (NOT = 1; two output tiles spill at 256 registers).  PW: the
-// rows' CSR metadata read two entries per LDS access (lds_row_spmm_w).
+// 62 % full); measured 178 vs 192 us per call (a workgroup with twice the
+// channels takes nearly twice as long).  ONE [M][16] slot: a step gathers T_k
+// from it, each lane keeps T_{k-1} of its own rows in registers, a barrier, the
+// lane swaps its rows' T_k out for T_{k+1}, a barrier.  SpMM lanes: (row lane /
+// 4 of a 16-row half tile, channels 4 (lane % 4) ..); MFMA lanes: (row j,
+// channels 8hh .. 8hh+7).  Fout <= 32 only (NOT = 1; two output tiles spill at
+// 256 registers).  PW: rows' CSR metadata read two per LDS access (lds_row_spmm_w).
 template <int NOT, bool PW>
 __global__ __launch_bounds__(kGT) void k_grp16_fwd(GrpFwdArgs A) {
 #pragma clang fp contract(off)
@@ -877,30 +878,16 @@ hipError_t launch_grp_fwd(const int* rowptr, const int* col, const float* val, c
   a.dbg = (debug_flags() >> 24) & 0xff;
 #endif
   const size_t lds = g16 ? grp16_fwd_lds(M, K, Fout, nnz) : grp_fwd_lds(M, K, Fout, nnz);
+  void (*k)(GrpFwdArgs) = &k_grp_fwd<2>;
   if (g16 && Fout <= 32) {
-    static hipError_t at = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_grp16_fwd<1, true>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    if (at != hipSuccess) return at;
+    k = &k_grp16_fwd<1, true>;
 #ifdef CG_DEBUG
-    static hipError_t at0 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_grp16_fwd<1, false>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    if (at0 != hipSuccess) return at0;
-    if (!spmm_pw()) hipLaunchKernelGGL((k_grp16_fwd<1, false>), dim3(grp_grid(N, G)), dim3(kGT), lds, s, a);
-    else
+    if (!spmm_pw()) k = &k_grp16_fwd<1, false>;
 #endif
-    hipLaunchKernelGGL((k_grp16_fwd<1, true>), dim3(grp_grid(N, G)), dim3(kGT), lds, s, a);
   } else if (Fout <= 32) {
-    static hipError_t at = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_grp_fwd<1>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    if (at != hipSuccess) return at;
-    hipLaunchKernelGGL(k_grp_fwd<1>, dim3(grp_grid(N, G)), dim3(kGT), lds, s, a);
-  } else {
-    static hipError_t at = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_grp_fwd<2>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    if (at != hipSuccess) return at;
-    hipLaunchKernelGGL(k_grp_fwd<2>, dim3(grp_grid(N, G)), dim3(kGT), lds, s, a);
+    k = &k_grp_fwd<1>;
   }
-  hipError_t e = hipGetLastError();
+  hipError_t e = launch_big_lds(k, dim3(grp_grid(N, G)), dim3(kGT), lds, s, a);
   if (e != hipSuccess || !y) return e;
   const int64_t n = int64_t(N) * M * Fout;
   const bool a16 = ((reinterpret_cast<uintptr_t>(yp) | reinterpret_cast<uintptr_t>(res) |
@@ -928,22 +915,13 @@ hipError_t launch_grp_clen(const int* trowptr, const int* tcol, const float* tva
   const int G = Fin / kGQ;
   GrpClenArgs a{trowptr, tcol, tval, order, M, rup(M + 1, 32), Fin, K, N, int(nnzT), G, D,
                 int64_t(N) * M * Fin, dx, dx_acc};
-  static hipError_t at1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_grp_clen<true>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-  if (at1 != hipSuccess) return at1;
+  void (*k)(GrpClenArgs) = &k_grp_clen<true>;
 #ifdef CG_DEBUG
   // CG_OPT_GRP_PC = 0 (ablation build only): columns read from LDS every step
   // (dx bitwise the same; lost its A/B, profiles/r04_r)
-  static hipError_t at0 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_grp_clen<false>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-  if (at0 != hipSuccess) return at0;
-  if (option(kOptGrpPc) == 0) {
-    hipLaunchKernelGGL(k_grp_clen<false>, dim3(grp_grid(N, G)), dim3(kGT), grp_clen_lds(M, nnzT), s, a);
-    return hipGetLastError();
-  }
+  if (option(kOptGrpPc) == 0) k = &k_grp_clen<false>;
 #endif
-  hipLaunchKernelGGL(k_grp_clen<true>, dim3(grp_grid(N, G)), dim3(kGT), grp_clen_lds(M, nnzT), s, a);
-  return hipGetLastError();
+  return launch_big_lds(k, dim3(grp_grid(N, G)), dim3(kGT), grp_clen_lds(M, nnzT), s, a);
 }
 
 // the fused variant serves Fout 2, 32 and 64 (the row GEMM's inner split
@@ -974,24 +952,9 @@ hipError_t launch_grp_clen_dy(const int* trowptr, const int* tcol, const float* 
   a.ts = g_debug_ts;
   a.dbg = (debug_flags() >> 24) & 0xff;
 #endif
-  static hipError_t at16 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_grp_clen_dy<16>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-  static hipError_t at32 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_grp_clen_dy<32>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
   const size_t lds = grp_clen_dy_lds(M, nnzT, K, Fout);
-  static hipError_t at1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_grp_clen_dy<1>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-  if (Fout == 2) {
-    if (at1 != hipSuccess) return at1;
-    hipLaunchKernelGGL(k_grp_clen_dy<1>, dim3(grp_grid(N, G)), dim3(kGT), lds, s, a);
-  } else if (Fout == 32) {
-    if (at16 != hipSuccess) return at16;
-    hipLaunchKernelGGL(k_grp_clen_dy<16>, dim3(grp_grid(N, G)), dim3(kGT), lds, s, a);
-  } else {
-    if (at32 != hipSuccess) return at32;
-    hipLaunchKernelGGL(k_grp_clen_dy<32>, dim3(grp_grid(N, G)), dim3(kGT), lds, s, a);
-  }
-  return hipGetLastError();
+  const auto k = Fout == 2 ? &k_grp_clen_dy<1> : Fout == 32 ? &k_grp_clen_dy<16> : &k_grp_clen_dy<32>;
+  return launch_big_lds(k, dim3(grp_grid(N, G)), dim3(kGT), lds, s, a);
 }
 
 }  // namespace cg

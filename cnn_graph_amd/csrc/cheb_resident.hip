@@ -44,6 +44,7 @@
 #include <type_traits>
 
 #include "cg_internal.h"
+#include "launch.h"
 
 namespace cg {
 namespace {
@@ -413,27 +414,14 @@ __global__ __launch_bounds__(kT) void cheb_bwd_resident(ResidentBwdArgs A) {
   }
 }
 
-template <typename Kern>
-hipError_t allow_big_lds(Kern k) {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-}
-
 template <int RPT, int MAXNNZ, int NT, bool FIN1>
 hipError_t launch_fwd_t(const ResidentGeom& g, int N, const ResidentFwdArgs& a, hipStream_t s) {
-  static hipError_t attr = allow_big_lds(&cheb_fwd_resident<RPT, MAXNNZ, NT, FIN1>);
-  if (attr != hipSuccess) return attr;
-  hipLaunchKernelGGL((cheb_fwd_resident<RPT, MAXNNZ, NT, FIN1>), dim3(N), dim3(kT), g.fwd_lds, s,
-                     a);
-  return hipGetLastError();
+  return launch_big_lds(&cheb_fwd_resident<RPT, MAXNNZ, NT, FIN1>, dim3(N), dim3(kT), g.fwd_lds, s, a);
 }
 
 template <int RPT, int MAXNNZ, bool FIN1>
 hipError_t launch_bwd_t(const ResidentGeom& g, int N, const ResidentBwdArgs& a, hipStream_t s) {
-  static hipError_t attr = allow_big_lds(&cheb_bwd_resident<RPT, MAXNNZ, FIN1>);
-  if (attr != hipSuccess) return attr;
-  hipLaunchKernelGGL((cheb_bwd_resident<RPT, MAXNNZ, FIN1>), dim3(N), dim3(kT), g.bwd_lds, s, a);
-  return hipGetLastError();
+  return launch_big_lds(&cheb_bwd_resident<RPT, MAXNNZ, FIN1>, dim3(N), dim3(kT), g.bwd_lds, s, a);
 }
 
 }  // namespace

@@ -21,7 +21,7 @@
 // The SpMM accumulates sequentially in CSR order with fp contraction off, so
 // the basis is bit-identical to the resident path and to lib/graph.py::chebyshev.
 #include "cg_internal.h"
-#include "occupancy_cache.h"
+#include "launch.h"
 #include "split_bf16.h"
 
 #include <algorithm>
@@ -1318,12 +1318,7 @@ hipError_t launch_dw_small(const float* basis, const float* dy, int64_t R, int F
   const int rpc = (kDwsStage - 64) / ((FinK + Fout) * 4);
   const size_t red = size_t(FinK) * Fout * (kDwsT + 1 + kDwsSeg) * 4;  // <= 64 x 545 x 4 = 140 KB
   const size_t lds = red > size_t(kDwsStage) ? red : size_t(kDwsStage);
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dw_small),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                     kLdsBytes);
-  if (attr != hipSuccess) return attr;
-  hipLaunchKernelGGL(k_dw_small, dim3(1), dim3(kDwsT), lds, s, basis, dy, R, FinK, Fout, rpc, out);
-  return hipGetLastError();
+  return launch_big_lds(&k_dw_small, dim3(1), dim3(kDwsT), lds, s, basis, dy, R, FinK, Fout, rpc, out);
 }
 
 hipError_t launch_cheb_step(const int* rowptr, const int* col, const float* val, const int* rperm,
@@ -1339,23 +1334,13 @@ hipError_t launch_cheb_step(const int* rowptr, const int* col, const float* val,
   // up to the CU's whole LDS: the per-lane scattered basis stores of
   // k_cheb_step<., true> are ~10x slower (config R's 32 x 20 hidden layers:
   // 835 us per call, profiles/r02_resgnn)
-  static const hipError_t attr4 = hipFuncSetAttribute(
-      reinterpret_cast<const void*>(&k_cheb_last<4>), hipFuncAttributeMaxDynamicSharedMemorySize,
-      kLdsBytes);
-  static const hipError_t attr1 = hipFuncSetAttribute(
-      reinterpret_cast<const void*>(&k_cheb_last<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-      kLdsBytes);
-  if (last && stage <= size_t(kLdsBytes) && attr4 == hipSuccess && attr1 == hipSuccess) {
-    if (vec == 4) hipLaunchKernelGGL((k_cheb_last<4>), grid, block, stage, s, a, g);
-    else hipLaunchKernelGGL((k_cheb_last<1>), grid, block, stage, s, a, g);
-  } else if (vec == 4) {
-    if (last) hipLaunchKernelGGL((k_cheb_step<4, true>), grid, block, 0, s, a, g);
-    else hipLaunchKernelGGL((k_cheb_step<4, false>), grid, block, 0, s, a, g);
-  } else {
-    if (last) hipLaunchKernelGGL((k_cheb_step<1, true>), grid, block, 0, s, a, g);
-    else hipLaunchKernelGGL((k_cheb_step<1, false>), grid, block, 0, s, a, g);
-  }
-  return hipGetLastError();
+  const auto staged = vec == 4 ? &k_cheb_last<4> : &k_cheb_last<1>;
+  if (last && stage <= size_t(kLdsBytes) && allow_big_lds(kernel_ptr(staged)) == hipSuccess)
+    return launch(staged, grid, block, stage, s, a, g);
+  // [vec == 4][last]
+  static constexpr decltype(staged) step[2][2] = {{&k_cheb_step<1, false>, &k_cheb_step<1, true>},
+                                                  {&k_cheb_step<4, false>, &k_cheb_step<4, true>}};
+  return launch(step[vec == 4][last], grid, block, 0, s, a, g);
 }
 
 hipError_t launch_clenshaw(const int* trowptr, const int* tcol, const float* tval, const int* rperm,
@@ -1365,9 +1350,7 @@ hipError_t launch_clenshaw(const int* trowptr, const int* tcol, const float* tva
   const int vec = step_vec(Fin);
   const StepGeom g = step_geom(N, M, Fin, vec);
   const dim3 grid(g.grid), block(256);
-  if (vec == 4) hipLaunchKernelGGL((k_clenshaw_step<4>), grid, block, 0, s, a, g);
-  else hipLaunchKernelGGL((k_clenshaw_step<1>), grid, block, 0, s, a, g);
-  return hipGetLastError();
+  return launch(vec == 4 ? &k_clenshaw_step<4> : &k_clenshaw_step<1>, grid, block, 0, s, a, g);
 }
 
 static int rowgemm_kc2(int Kc) {
@@ -1387,7 +1370,7 @@ hipError_t launch_rowgemm(const float* A, int64_t R, int Kc, int lda, const floa
                           int64_t bs_j, int64_t bs_p, int planes, int Nc, float* C, int ldc,
                           int64_t c_plane, hipStream_t s, const float* res, int act, int pfin,
                           int apl_fin, int64_t apl_stride, int bmapK) {
-  if (pfin > 0 && (planes != 1 || res || act)) return hipErrorInvalidValue;
+  if (Nc < 1 || (pfin > 0 && (planes != 1 || res || act))) return hipErrorInvalidValue;
   if (apl_fin > 0 && (apl_fin % 16 != 0 || apl_stride % 4 != 0 || Kc < 32 || planes != 1 ||
                       pfin > 0 || bmapK < 1))
     return hipErrorInvalidValue;
@@ -1398,99 +1381,46 @@ hipError_t launch_rowgemm(const float* A, int64_t R, int Kc, int lda, const floa
                 apl_fin, apl_stride, bmapK};
   const int NT = (Nc + 31) / 32;
   const int64_t ntiles = (R + 127) / 128;
+  const int nt = NT < 8 ? NT : 8;
+  void* args[] = {&a};
   if (option(kOptGemmX3) != 0 && NT <= 8) {
     // the split-bf16 form: B_p's three terms in LDS, [k-block][tile][term][lane] x 16 B
     const size_t lx = size_t((Kc + 15) / 16) * NT * 3 * 64 * 16;
     if (lx <= size_t(kLdsBytes)) {
-      const void* k = nullptr;
-      switch (NT) {
-#define CG_RGX(n) \
-  case n: k = reinterpret_cast<const void*>(&k_rowgemm_x3<n>); break;
-        CG_RGX(1) CG_RGX(2) CG_RGX(3) CG_RGX(4) CG_RGX(5) CG_RGX(6) CG_RGX(7) default: CG_RGX(8)
-#undef CG_RGX
+      static constexpr decltype(&k_rowgemm_x3<1>) kx[8] = {
+          &k_rowgemm_x3<1>, &k_rowgemm_x3<2>, &k_rowgemm_x3<3>, &k_rowgemm_x3<4>,
+          &k_rowgemm_x3<5>, &k_rowgemm_x3<6>, &k_rowgemm_x3<7>, &k_rowgemm_x3<8>};
+      const void* k = kernel_ptr(kx[nt - 1]);
+      if (lx > size_t(64) * 1024) {
+        const hipError_t attr = allow_big_lds(k);
+        if (attr != hipSuccess) return attr;
       }
-      int dev = 0;
-      (void)hipGetDevice(&dev);
-      static ResidentCache xcache;
-      const int res_blocks = xcache.get(dev, k, 256, lx, [&](const void* kf, int thr, size_t l, int* per_cu,
-                                                             int* cus) {
-        (void)hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kf, thr, l) == hipSuccess &&
-               hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess;
-      });
+      const int res_blocks = resident_blocks(k, 256, lx);
       const dim3 grid(persistent_grid(ntiles, res_blocks, planes), unsigned(planes)), block(256);
-      void* args[] = {&a};
       return hipLaunchKernel(k, grid, block, args, lx, s);
     }
   }
   const size_t lds = size_t(2) * a.KC2 * NT * 32 * 4;
   // every chunk 16 contiguous in-range floats, at least 3 of them per half
   const bool pf = a.vecA && a.KC2 % 16 == 0 && 2 * a.KC2 <= Kc && a.KC2 / 16 >= 3;
+  // [pf][column tiles - 1]
+  static constexpr decltype(&k_rowgemm<1, false>) kg[2][8] = {
+      {&k_rowgemm<1, false>, &k_rowgemm<2, false>, &k_rowgemm<3, false>, &k_rowgemm<4, false>,
+       &k_rowgemm<5, false>, &k_rowgemm<6, false>, &k_rowgemm<7, false>, &k_rowgemm<8, false>},
+      {&k_rowgemm<1, true>, &k_rowgemm<2, true>, &k_rowgemm<3, true>, &k_rowgemm<4, true>,
+       &k_rowgemm<5, true>, &k_rowgemm<6, true>, &k_rowgemm<7, true>, &k_rowgemm<8, true>}};
+  const void* k = kernel_ptr(kg[pf][nt - 1]);
+  if (lds > size_t(64) * 1024) {
+    const hipError_t attr = allow_big_lds(k);
+    if (attr != hipSuccess) return attr;
+  }
   // the persistent blocks: as many as are resident at once (a grid beyond that
   // runs its last blocks as a tail at a fraction of the chip: config D's y GEMM
   // had 1 024 blocks for 768 resident slots), at most 1 024
-  unsigned gx;
-  {
-    const int nt = NT < 8 ? NT : 8;
-    const void* k = nullptr;
-#define CG_RGK(n)                                                                              \
-  case n:                                                                                      \
-    k = pf ? reinterpret_cast<const void*>(&k_rowgemm<n, true>)                                \
-           : reinterpret_cast<const void*>(&k_rowgemm<n, false>);                              \
-    break;
-    switch (nt) { CG_RGK(1) CG_RGK(2) CG_RGK(3) CG_RGK(4) CG_RGK(5) CG_RGK(6) CG_RGK(7) default: CG_RGK(8) }
-#undef CG_RGK
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    // keyed on (device, kernel, threads, dynamic LDS): the LDS follows Kc
-    static ResidentCache cache;
-    const int res_blocks = cache.get(dev, k, 256, lds, [&](const void* kf, int thr, size_t l, int* per_cu,
-                                                           int* cus) {
-      if (l > size_t(64) * 1024)
-        (void)hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-      return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kf, thr, l) == hipSuccess &&
-             hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess;
-    });
-    gx = persistent_grid(ntiles, res_blocks, planes);
-  }
-  const dim3 grid(gx, unsigned(planes)), block(256);
-  if (lds > size_t(64) * 1024) {
-    // once per process, thread-safe (a function-local static's initialiser)
-    static const hipError_t attr = [] {
-      const void* ks[16] = {reinterpret_cast<const void*>(&k_rowgemm<1, false>),
-                            reinterpret_cast<const void*>(&k_rowgemm<2, false>),
-                            reinterpret_cast<const void*>(&k_rowgemm<3, false>),
-                            reinterpret_cast<const void*>(&k_rowgemm<4, false>),
-                            reinterpret_cast<const void*>(&k_rowgemm<5, false>),
-                            reinterpret_cast<const void*>(&k_rowgemm<6, false>),
-                            reinterpret_cast<const void*>(&k_rowgemm<7, false>),
-                            reinterpret_cast<const void*>(&k_rowgemm<8, false>),
-                            reinterpret_cast<const void*>(&k_rowgemm<1, true>),
-                            reinterpret_cast<const void*>(&k_rowgemm<2, true>),
-                            reinterpret_cast<const void*>(&k_rowgemm<3, true>),
-                            reinterpret_cast<const void*>(&k_rowgemm<4, true>),
-                            reinterpret_cast<const void*>(&k_rowgemm<5, true>),
-                            reinterpret_cast<const void*>(&k_rowgemm<6, true>),
-                            reinterpret_cast<const void*>(&k_rowgemm<7, true>),
-                            reinterpret_cast<const void*>(&k_rowgemm<8, true>)};
-      for (const void* k : ks) {
-        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        if (e != hipSuccess) return e;
-      }
-      return hipSuccess;
-    }();
-    if (attr != hipSuccess) return attr;
-  }
-#define CG_RG(nt)                                                                 \
-  case nt:                                                                        \
-    if (pf) hipLaunchKernelGGL((k_rowgemm<nt, true>), grid, block, lds, s, a);    \
-    else hipLaunchKernelGGL((k_rowgemm<nt, false>), grid, block, lds, s, a);      \
-    break;
-  switch (NT < 8 ? NT : 8) {
-    CG_RG(1) CG_RG(2) CG_RG(3) CG_RG(4) CG_RG(5) CG_RG(6) CG_RG(7)
-    default: CG_RG(8)
-  }
-#undef CG_RG
+  // (the count is keyed on (device, kernel, threads, dynamic LDS): the LDS follows Kc)
+  const dim3 grid(persistent_grid(ntiles, resident_blocks(k, 256, lds), planes), unsigned(planes)),
+      block(256);
+  (void)hipLaunchKernel(k, grid, block, args, lds, s);
   return hipGetLastError();
 }
 
@@ -1511,19 +1441,12 @@ hipError_t launch_gemm_f32(bool trans_a, bool trans_b, int Mg, int Ng, int Kg, c
   const int kchunk = gemm_kchunk(Kg, splits);
   const int nsplit = gemm_effective_splits(Kg, splits);
   const dim3 grid((Mg + 63) / 64, (Ng + 63) / 64, nsplit > 0 ? nsplit : 1);
-  if (!trans_a && !trans_b)
-    hipLaunchKernelGGL((k_gemm_f32<false, false>), grid, dim3(256), 0, s, Mg, Ng, Kg, A, lda, B,
-                       ldb, C, ldc, kchunk, remapK);
-  else if (!trans_a && trans_b)
-    hipLaunchKernelGGL((k_gemm_f32<false, true>), grid, dim3(256), 0, s, Mg, Ng, Kg, A, lda, B,
-                       ldb, C, ldc, kchunk, remapK);
-  else if (trans_a && !trans_b)
-    hipLaunchKernelGGL((k_gemm_f32<true, false>), grid, dim3(256), 0, s, Mg, Ng, Kg, A, lda, B,
-                       ldb, C, ldc, kchunk, remapK);
-  else
-    hipLaunchKernelGGL((k_gemm_f32<true, true>), grid, dim3(256), 0, s, Mg, Ng, Kg, A, lda, B, ldb,
-                       C, ldc, kchunk, remapK);
-  return hipGetLastError();
+  // [trans_a][trans_b]
+  static constexpr decltype(&k_gemm_f32<false, false>) kerns[2][2] = {
+      {&k_gemm_f32<false, false>, &k_gemm_f32<false, true>},
+      {&k_gemm_f32<true, false>, &k_gemm_f32<true, true>}};
+  return launch(kerns[trans_a][trans_b], grid, dim3(256), 0, s, Mg, Ng, Kg, A, lda, B,
+                ldb, C, ldc, kchunk, remapK);
 }
 
 int dw_chunks(int64_t R) {
@@ -1688,20 +1611,12 @@ static hipError_t launch_dw_slabs_cols(const float* basis, const float* dy, int6
   const size_t lds = size_t(kDwRB) * ((span | 1) + (((Fout + 31) & ~31) | 1)) * 4;
   const dim3 grid(chunks, groups);
   // 8 waves per block unless CG_OPT_DW_WAVES = 4 (A/B runs; the slabs are the same)
-  const int nw = option(kOptDwWaves);
-  if (vw == 4 && nw == 8)
-    hipLaunchKernelGGL((k_dw_slabs<4, 8>), grid, dim3(512), lds, s, basis, dy, R, FinK, Fout, rpc,
-                       slab, pl_fin, pl_stride, K, tpb, xb, x_fin, x_stride, FinKh, ldd);
-  else if (vw == 4)
-    hipLaunchKernelGGL((k_dw_slabs<4, 4>), grid, dim3(256), lds, s, basis, dy, R, FinK, Fout, rpc,
-                       slab, pl_fin, pl_stride, K, tpb, xb, x_fin, x_stride, FinKh, ldd);
-  else if (nw == 8)
-    hipLaunchKernelGGL((k_dw_slabs<1, 8>), grid, dim3(512), lds, s, basis, dy, R, FinK, Fout, rpc,
-                       slab, pl_fin, pl_stride, K, tpb, xb, x_fin, x_stride, FinKh, ldd);
-  else
-    hipLaunchKernelGGL((k_dw_slabs<1, 4>), grid, dim3(256), lds, s, basis, dy, R, FinK, Fout, rpc,
-                       slab, pl_fin, pl_stride, K, tpb, xb, x_fin, x_stride, FinKh, ldd);
-  return hipGetLastError();
+  const bool w8 = option(kOptDwWaves) == 8;
+  // [vw == 4][8 waves]
+  static constexpr decltype(&k_dw_slabs<1, 4>) kerns[2][2] = {{&k_dw_slabs<1, 4>, &k_dw_slabs<1, 8>},
+                                                              {&k_dw_slabs<4, 4>, &k_dw_slabs<4, 8>}};
+  return launch(kerns[vw == 4][w8], grid, dim3(w8 ? 512 : 256), lds, s, basis, dy, R,
+                FinK, Fout, rpc, slab, pl_fin, pl_stride, K, tpb, xb, x_fin, x_stride, FinKh, ldd);
 }
 
 hipError_t launch_dw_slabs(const float* basis, const float* dy, int64_t R, int FinKh, int Fout,

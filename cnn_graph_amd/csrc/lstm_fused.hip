@@ -31,6 +31,7 @@
 // Bound: the fp32 contraction, 2*M*(K*32)*128 FLOP per sample and step, on
 // MFMA (157 TF/s peak) -- with config E's K = 3, 25 MFLOP per sample.
 #include "cg_internal.h"
+#include "launch.h"
 #include "lstm_gates.h"
 
 namespace cg {
@@ -256,14 +257,9 @@ hipError_t launch_lstm_hstep(int gates, int N, int M, int K, const int* rowptr, 
                              float* h_out, float* act, float* planes, int64_t plane,
                              hipStream_t s) {
   if (!lstm_hstep_ok(M, kH, K) || N < 1) return hipErrorInvalidValue;
-  static hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lstm_hstep),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               kLdsBytes);
-  if (attr != hipSuccess) return attr;
   HStepArgs a{rowptr, col, val, M, K, N, gates, N % 8 == 0 ? 1 : 0, h_prev, c_prev, gx, Wh, bias,
               c_out, h_out, act, planes, plane};
-  hipLaunchKernelGGL(k_lstm_hstep, dim3(2 * N), dim3(kHT), lstm_hstep_lds(M, K), s, a);
-  return hipGetLastError();
+  return launch_big_lds(&k_lstm_hstep, dim3(2 * N), dim3(kHT), lstm_hstep_lds(M, K), s, a);
 }
 
 }  // namespace cg

@@ -56,6 +56,7 @@
 //   units.  The h-weight gradient is summed afterwards per Chebyshev order
 //   over all steps from the forward's planes (one GEMM per order).
 #include "cg_internal.h"
+#include "launch.h"
 #include "split_bf16.h"
 #include "lds_spmm.h"
 #include "lstm_gates.h"
@@ -1131,10 +1132,8 @@ bool lstm_bstep_ok(int M, int H, int K, int64_t nnzT) {
 }
 
 int lstm_seq_pairs(int N, int device) {
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess ||
-      cus < 2)
-    cus = 256;
+  int cus = device_cus(device);
+  if (cus < 2) cus = 256;
   const int p = cus / 2;
   return N < p ? N : p;
 }
@@ -1148,26 +1147,9 @@ hipError_t launch_lstm_seq(int gates, int T, int N, int M, int K, int64_t nnz, c
   if (!lstm_seq_ok(M, kH, K, nnz, xs ? Fin : 0) || N < 1 || T < 1 || P < 1 || P > N ||
       (xs && (Fin < 1 || Fin > 8 || !Wx || !xplanes)) || (!xs && !gx))
     return hipErrorInvalidValue;
-  // the kernel's static LDS (the abort word) counts against the same 160 KB
-  // [xpre][reference gates]
-  static void (*const kerns[2][2])(SeqArgs) = {{&k_lstm_seq<false, false>, &k_lstm_seq<false, true>},
-                                               {&k_lstm_seq<true, false>, &k_lstm_seq<true, true>}};
-  static const hipError_t attr = [] {
-    for (auto& row : kerns)
-      for (auto* k : row) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 kLdsBytes - kSeqStaticLds);
-        if (e != hipSuccess) return e;
-      }
-    return hipSuccess;
-  }();
-  if (attr != hipSuccess) return attr;
-  int dev = 0, rate_khz = 0;
-  (void)hipGetDevice(&dev);
-  if (hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess ||
-      rate_khz <= 0)
-    rate_khz = 100000;  // 100 MHz
+  const int dev = current_device();  // read once for every lookup below
+  int rate_khz = device_wall_clock_khz(dev);
+  if (rate_khz <= 0) rate_khz = 100000;  // 100 MHz
   SeqArgs a{rowptr, col, val, order, M, round_up(M + 1, 32), K, N, T, gates, int(nnz), P,
             P % 8 == 0 ? 1 : 0, gx, xs, Wx, xplanes, xpstride, Fin, Wh, bias, h0, c0, hs, cs, act, planes, pstride, flags, status,
             // a pair hand-off that has not happened after 2 s ends the launch
@@ -1190,29 +1172,14 @@ hipError_t launch_lstm_seq(int gates, int T, int N, int M, int K, int64_t nnz, c
     static void (*const xk[2][3])(const int*, const int*, const float*, int, int, int, const float*,
                                   float*, int64_t) = {{&k_xbasis<1, 2>, &k_xbasis<1, 3>, &k_xbasis<1, 4>},
                                                       {&k_xbasis<2, 2>, &k_xbasis<2, 3>, &k_xbasis<2, 4>}};
-    static const hipError_t xat = [] {
-      for (auto& row : xk)
-        for (auto* k : row) {
-          const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-          if (e != hipSuccess) return e;
-        }
-      return hipSuccess;
-    }();
-    if (xat != hipSuccess) return xat;
     auto* xkern = xk[Fin - 1][K - 2];
     const int S = T * N;
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-      cus = 256;
-    int per_cu = 1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(xkern),
-                                                     kXT, xb_lds) != hipSuccess || per_cu < 1)
-      per_cu = 1;
-    const int spw = (S + per_cu * cus - 1) / (per_cu * cus);  // every workgroup resident
-    hipLaunchKernelGGL(xkern, dim3((S + spw - 1) / spw), dim3(kXT), xb_lds, s, rowptr, col, val, M,
-                       S, spw, xs, xplanes, xpstride);
-    e = hipGetLastError();
+    e = allow_big_lds(kernel_ptr(xkern), kLdsBytes, dev);
+    if (e != hipSuccess) return e;
+    const int slots = xbasis_resident(resident_blocks(kernel_ptr(xkern), kXT, xb_lds, dev));
+    const int spw = (S + slots - 1) / slots;  // every workgroup resident
+    e = launch(xkern, dim3((S + spw - 1) / spw), dim3(kXT), xb_lds, s, rowptr, col, val, M, S, spw,
+               xs, xplanes, xpstride);
     if (e != hipSuccess) return e;
     a.xpre = 1;
   } else if (xs && seq_xpre()) {
@@ -1236,17 +1203,20 @@ hipError_t launch_lstm_seq(int gates, int T, int N, int M, int K, int64_t nnz, c
   // other streams or processes can hold CUs, which is what the hand-off
   // timeout, the NaN poisoning and the plan's fault word are for
   const size_t lds = lstm_seq_lds(M, K, nnz, xs ? Fin : 0);
-  void (*const kfn)(SeqArgs) = kerns[a.xpre ? 1 : 0][gates == 0 ? 1 : 0];
-  const void* kern = reinterpret_cast<const void*>(kfn);
-  int per_cu = 0, cus = 0;
-  e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kST, lds);
+  // [xpre][reference gates]
+  static constexpr decltype(&k_lstm_seq<false, false>) kerns[2][2] = {
+      {&k_lstm_seq<false, false>, &k_lstm_seq<false, true>},
+      {&k_lstm_seq<true, false>, &k_lstm_seq<true, true>}};
+  const auto kfn = kerns[a.xpre ? 1 : 0][gates == 0 ? 1 : 0];
+  // the kernel's static LDS (the abort word) counts against the same 160 KB
+  e = allow_big_lds(kernel_ptr(kfn), kLdsBytes - kSeqStaticLds, dev);
   if (e != hipSuccess) return e;
-  e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (e != hipSuccess) return e;
-  if (per_cu < 1 || 2 * P > per_cu * cus) return hipErrorCooperativeLaunchTooLarge;
-  const dim3 grid(2 * P), block(kST);
-  hipLaunchKernelGGL(kfn, grid, block, lds, s, a);
-  return hipGetLastError();
+  switch (grid_fit(2 * P, resident_blocks(kernel_ptr(kfn), kST, lds, dev))) {
+    case kGridUnknown: return hipErrorUnknown;
+    case kGridTooLarge: return hipErrorCooperativeLaunchTooLarge;
+    case kGridFits: break;
+  }
+  return launch(kfn, dim3(2 * P), dim3(kST), lds, s, a);
 }
 
 hipError_t launch_lstm_bstep(int gates, int N, int M, int K, const int* trowptr, const int* tcol,
@@ -1264,30 +1234,11 @@ hipError_t launch_lstm_bstep(int gates, int N, int M, int K, const int* trowptr,
   // the split-bf16 D_k contraction (CG_OPT_GEMM_X3) where its larger W image fits
   const bool x3 = option(kOptGemmX3) != 0 && lstm_bstep_lds(M, K, nnzT, true) <= size_t(kLdsBytes);
   const size_t lds = lstm_bstep_lds(M, K, nnzT, x3);
-#define CG_BSTEP(KK)                                                                              \
-  case KK: {                                                                                      \
-    static hipError_t at = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lstm_bstep<KK, false>), \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize,       \
-                                               kLdsBytes);                                        \
-    static hipError_t atx = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lstm_bstep<KK, true>), \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize,      \
-                                                kLdsBytes);                                       \
-    if (at != hipSuccess) return at;                                                              \
-    if (atx != hipSuccess) return atx;                                                            \
-    if (x3) hipLaunchKernelGGL((k_lstm_bstep<KK, true>), dim3(2 * N), dim3(kST), lds, s, a);      \
-    else hipLaunchKernelGGL((k_lstm_bstep<KK, false>), dim3(2 * N), dim3(kST), lds, s, a);        \
-    break;                                                                                        \
-  }
-  switch (K) {
-    CG_BSTEP(1)
-    CG_BSTEP(2)
-    CG_BSTEP(3)
-    CG_BSTEP(4)
-    default:
-      return hipErrorInvalidValue;
-  }
-#undef CG_BSTEP
-  return hipGetLastError();
+  // [x3][K - 1]; lstm_bstep_ok admits K 1 .. 4
+  static constexpr decltype(&k_lstm_bstep<1, false>) kerns[2][4] = {
+      {&k_lstm_bstep<1, false>, &k_lstm_bstep<2, false>, &k_lstm_bstep<3, false>, &k_lstm_bstep<4, false>},
+      {&k_lstm_bstep<1, true>, &k_lstm_bstep<2, true>, &k_lstm_bstep<3, true>, &k_lstm_bstep<4, true>}};
+  return launch_big_lds(kerns[x3][K - 1], dim3(2 * N), dim3(kST), lds, s, a);
 }
 
 }  // namespace cg
