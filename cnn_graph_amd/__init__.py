@@ -14,7 +14,16 @@ Modules
   filter      functional cheby_conv (lib/filter.py API)
   coarsening  graph coarsening + perm_data (lib/coarsening.py API)
   dist        one-process-per-GPU data parallelism (RCCL all-reduce)
+  glstm_period  GLSTMPeriodModel: the closeness / period / trend gconv-LSTM networks
 """
 __version__ = "0.1.0"
 
-__all__ = ["graph", "plan", "ops", "graph_conv", "filter", "coarsening", "dist"]
+__all__ = ["graph", "plan", "ops", "graph_conv", "filter", "coarsening", "dist", "GLSTMPeriodModel"]
+
+
+def __getattr__(name):
+    # the model class, imported on first use (importing the package stays free of torch)
+    if name == "GLSTMPeriodModel":
+        from .glstm_period import GLSTMPeriodModel
+        return GLSTMPeriodModel
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

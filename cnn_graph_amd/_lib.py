@@ -43,6 +43,7 @@ _c_int, _c_i32, _c_i64, _c_sz = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ct
 _vp, _fp = ctypes.c_void_p, ctypes.c_void_p  # device pointers are passed as void*
 _ip32 = ctypes.POINTER(ctypes.c_int32)
 _fp32 = ctypes.POINTER(ctypes.c_float)
+_pp = ctypes.POINTER(ctypes.c_void_p)  # a host array of device pointers
 
 _SIGNATURES = {
     "cg_version": ([], _c_int),
@@ -148,6 +149,14 @@ _SIGNATURES = {
     "cg_seq_xent_head": ([_vp, _vp, _vp, _vp, _c_i32, _c_i32, _c_i32, _c_i32, ctypes.c_float,
                           ctypes.c_uint64, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_sz,
                           _vp], _c_int),
+    # the branch seams: host arrays of B device pointers / sizes / seeds
+    "cg_branch_merge_forward": ([_c_i32, _c_i32, _c_i32, _c_i32, _pp, _pp, _vp, _vp], _c_int),
+    "cg_branch_merge_backward": ([_c_i32, _c_i32, _c_i32, _c_i32, _vp, _pp, _pp, _pp, _pp, _c_i32,
+                                  _vp], _c_int),
+    "cg_concat_drop_forward": ([_c_i32, _c_i32, _c_i32, _ip32, _pp, ctypes.c_float,
+                                ctypes.POINTER(ctypes.c_uint64), _vp, _vp], _c_int),
+    "cg_concat_drop_backward": ([_c_i32, _c_i32, _c_i32, _ip32, _vp, ctypes.c_float,
+                                 ctypes.POINTER(ctypes.c_uint64), _pp, _vp], _c_int),
     "cg_lstm_seq_x_supported": ([_vp, _c_i32, _c_i32, _c_i32, ctypes.POINTER(_c_i32)], _c_int),
     "cg_lstm_seq_forward_x": ([_vp, _c_i32, _c_i32, _c_i32, _c_i32, _c_i32, _c_i32, _vp, _vp, _vp,
                                _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _c_sz,

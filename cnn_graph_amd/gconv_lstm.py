@@ -762,6 +762,36 @@ def lstm_to_hT(cells, wrapped, xs, dropout: bool):
     return st.h, None
 
 
+def make_cells(L, feat_in, H, K, layer_count, lmax, gates, device, gen, filter, hconv="auto"):
+    """glstm_layer's cells (lib/gconv_lstm.py:609-627): layer_count GConvLSTMCells,
+    the first reading feat_in features, the others H; their initial values are
+    drawn from ``gen`` in creation order."""
+    return [GConvLSTMCell(H, laplacian=L, lmax=lmax, K=K, feat_in=feat_in if li == 0 else H,
+                          gates=gates, device=device, generator=gen, filter_type=filter, hconv=hconv)
+            for li in range(int(layer_count))]
+
+
+def carve_cells(trainer: FlatTrainer, cells, scope: str = ""):
+    """Move every cell's Wx, Wh, b into the trainer's flat buffers (the next
+    views ``carve`` hands out), as autograd-owned Parameters whose ``.grad`` is
+    the bucket view; ``scope`` prefixes the variable names."""
+    for li, c in enumerate(cells):
+        for n in ("Wx", "Wh", "b"):
+            t = getattr(c, n).detach()
+            name = f"{scope}gconv_lstm_layer/rnn/multi_rnn_cell/cell_{li}/{n}"
+            setattr(c, n, trainer.carve(t.shape, name, init=t)[0])
+
+
+def wrap_cells(cells, keep_prob, seed, comm, first: int = 0):
+    """Each cell in its DropoutWrapper(keep_prob) (the cell itself at keep_prob
+    1).  Each wrapper's mask stream comes from (model seed, rank, first + layer):
+    training is reproducible from the seed, and the ranks draw independent
+    masks for their shards (TF: one random op per wrapper per replica)."""
+    rank = int(getattr(comm, "rank", 0)) if comm is not None else 0
+    return [DropoutWrapper(c, keep_prob, seed=dropout_seed(seed, rank, first + li))
+            if keep_prob < 1.0 else c for li, c in enumerate(cells)]
+
+
 class LSTMStackTrainer(FlatTrainer):
     """The part ``GLSTMModel`` and ``GLSTMGconvModel`` share: ``glstm_layer``
     (lib/gconv_lstm.py:609-627) -- layer_count GConvLSTMCells, each in a
@@ -781,10 +811,7 @@ class LSTMStackTrainer(FlatTrainer):
         device = torch.device(device if device is not None else "cuda")
         self._gen = gen = torch.Generator(device=device)
         gen.manual_seed(seed)
-        cells = [GConvLSTMCell(self.H, laplacian=L, lmax=lmax, K=self.K,
-                               feat_in=self.F if li == 0 else self.H, gates=gates, device=device,
-                               generator=gen, filter_type=filter, hconv=hconv)
-                 for li in range(int(layer_count))]
+        cells = make_cells(L, self.F, self.H, self.K, layer_count, lmax, gates, device, gen, filter, hconv)
         self.M = cells[0]._nNode
         super().__init__(sum(p.numel() for c in cells for p in c.parameters()) + tail_numel,
                          (self.N, self.M, self.Fout), optimizer, learning_rate, decay_rate, decay_steps,
@@ -792,18 +819,9 @@ class LSTMStackTrainer(FlatTrainer):
         fourier = filter == "fourier_conv"
         self.plan = None if fourier else cells[0].plan
         self.U = cells[0].U if fourier else None
-        for li, c in enumerate(cells):
-            for n in ("Wx", "Wh", "b"):
-                t = getattr(c, n).detach()
-                name = f"gconv_lstm_layer/rnn/multi_rnn_cell/cell_{li}/{n}"
-                setattr(c, n, self.carve(t.shape, name, init=t)[0])
+        carve_cells(self, cells)
         self.cells = cells
-        # each wrapper's mask stream from (model seed, rank, layer): training is
-        # reproducible from the seed, and the ranks draw independent masks for
-        # their shards (TF: one random op per wrapper per replica)
-        rank = int(getattr(comm, "rank", 0)) if comm is not None else 0
-        self.wrapped = [DropoutWrapper(c, keep_prob, seed=dropout_seed(seed, rank, li))
-                        if keep_prob < 1.0 else c for li, c in enumerate(cells)]
+        self.wrapped = wrap_cells(cells, keep_prob, seed, comm)
 
     def _steps(self, x):
         if x.dim() == 3:  # [N, M, F*T] as the reference feeds it

@@ -1412,3 +1412,154 @@ def stack_merge(out_i, w_i, acc=None):
     """acc + relu(out_i) * w_i (w_i [M, F] broadcast over N; acc None: no add)
     -- one term of X = sum_i relu(net_i) * w_i, lib/graph_conv.py:292-301."""
     return _StackMerge.apply(out_i, w_i, acc)
+
+
+# -- the branch seams of the closeness / period / trend networks (lib/gconv_lstm.py:431-607) --
+MAX_BRANCHES = 4
+
+
+def _ptr_array(ts):
+    """A host array of device pointers (None entries = NULL) for the cg_branch_* / cg_concat_* calls."""
+    return (ctypes.c_void_p * len(ts))(*[_p(t) for t in ts])
+
+
+def _branches(name, ts, lead=None):
+    """The branches of one seam call: 1 .. MAX_BRANCHES fp32 device tensors
+    (made contiguous), every one [*lead, C_b] when ``lead`` is given."""
+    ts = list(ts)
+    if not 1 <= len(ts) <= MAX_BRANCHES:
+        raise ValueError(f"{name}: 1 to {MAX_BRANCHES} branches, got {len(ts)}")
+    for b, t in enumerate(ts):
+        _check_dev(f"{name}[{b}]", t)
+        if lead is not None and (t.dim() != len(lead) + 1 or tuple(t.shape[:-1]) != tuple(lead)):
+            raise ValueError(f"{name}[{b}] must be [{', '.join(map(str, lead))}, *], got {tuple(t.shape)}")
+    return [t.contiguous() for t in ts]
+
+
+def branch_merge_forward(ys, ws, out=None):
+    """cg_branch_merge_forward: ((y_0 w_0) + y_1 w_1) + ... with y_b [N, M, F]
+    and w_b [M, F] broadcast over N, every product and sum rounded in that order."""
+    ys = _branches("ys", ys)
+    N, M, F = (int(s) for s in ys[0].shape)
+    ys = _branches("ys", ys, (N, M))
+    ws = _branches("ws", ws, (M,))
+    if len(ws) != len(ys) or any(int(t.shape[-1]) != F for t in ys + ws):
+        raise ValueError(f"branch_merge: need as many w [{M}, {F}] as y [{N}, {M}, {F}]")
+    out = _out("out", out, (N, M, F), ys[0].device)
+    _lib.call("cg_branch_merge_forward", len(ys), N, M, F, _ptr_array(ys), _ptr_array(ws), _p(out),
+              _stream(ys[0]))
+    return out
+
+
+def branch_merge_backward(dout, ys, ws, need_dy=None, need_dw=None, out_dw=None,
+                          accumulate_dw: bool = False):
+    """cg_branch_merge_backward, ONE launch: (dys, dws) with dy_b = dout w_b and
+    dw_b (+)= sum_n dout y_b; need_dy / need_dw: per-branch flags (default all),
+    a False entry is skipped (None in its place).  out_dw: the tensors to write
+    (accumulate_dw: to add into)."""
+    ys = _branches("ys", ys)
+    N, M, F = (int(s) for s in ys[0].shape)
+    ws = _branches("ws", ws, (M,))
+    B = len(ys)
+    _check_dev("dout", dout)
+    dout = dout.contiguous()
+    if len(ws) != B or tuple(dout.shape) != (N, M, F):
+        raise ValueError(f"branch_merge_backward: need dout [{N}, {M}, {F}] and {B} weights")
+    need_dy = [True] * B if need_dy is None else list(need_dy)
+    need_dw = [True] * B if need_dw is None else list(need_dw)
+    dev = dout.device
+    dys = [torch.empty((N, M, F), device=dev, dtype=torch.float32) if need_dy[b] else None
+           for b in range(B)]
+    dws = [_out(f"out_dw[{b}]", out_dw[b] if out_dw is not None else None, (M, F), dev,
+                accumulate=accumulate_dw) if need_dw[b] else None for b in range(B)]
+    if any(need_dy) or any(need_dw):
+        _lib.call("cg_branch_merge_backward", B, N, M, F, _p(dout), _ptr_array(ys), _ptr_array(ws),
+                  _ptr_array(dys), _ptr_array(dws), int(bool(accumulate_dw)), _stream(dout))
+    return dys, dws
+
+
+class _BranchMerge(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, B, *yw):
+        ys, ws = yw[:B], yw[B:]
+        out = branch_merge_forward(ys, ws)
+        ctx.save_for_backward(*ys, *ws)
+        ctx.B = B
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        B, saved = ctx.B, ctx.saved_tensors
+        need = ctx.needs_input_grad[1:]
+        dys, dws = branch_merge_backward(dout, saved[:B], saved[B:], need[:B], need[B:])
+        return (None, *dys, *dws)
+
+
+def branch_merge(ys, ws):
+    """X = sum_b y_b * w_b as the reference graph chains it (lib/gconv_lstm.py
+    :494-497): ys B tensors [N, M, F], ws B tensors [M, F]; no activation.  The
+    backward is one launch for every branch (cg_branch_merge_backward)."""
+    ys, ws = list(ys), list(ws)
+    if len(ys) != len(ws):
+        raise ValueError("branch_merge: as many weights as branches")
+    return _BranchMerge.apply(len(ys), *ys, *ws)
+
+
+def _concat_args(hs, keep, seeds):
+    N, M = int(hs[0].shape[0]), int(hs[0].shape[1])
+    B = len(hs)
+    if not 0.0 < float(keep) <= 1.0:
+        raise ValueError(f"keep must be in (0, 1], got {keep}")
+    seeds = [0] * B if seeds is None else [int(s) & ((1 << 64) - 1) for s in seeds]
+    if len(seeds) != B:
+        raise ValueError("concat_drop: one seed per branch")
+    H = [int(t.shape[-1]) for t in hs]
+    return N, M, B, H, (ctypes.c_int32 * B)(*H), (ctypes.c_uint64 * B)(*seeds)
+
+
+def concat_drop_forward(hs, keep: float = 1.0, seeds=None, out=None):
+    """cg_concat_drop_forward: cat_b(dropout(h_b, keep, seed_b)) along the last
+    axis in one pass (seed_b already offset, as ``dropout``'s folded seed is)."""
+    hs = _branches("hs", hs)
+    hs = _branches("hs", hs, tuple(hs[0].shape[:2]))
+    N, M, B, H, Hc, sc = _concat_args(hs, keep, seeds)
+    out = _out("out", out, (N, M, sum(H)), hs[0].device)
+    _lib.call("cg_concat_drop_forward", B, N, M, Hc, _ptr_array(hs), float(keep), sc, _p(out),
+              _stream(hs[0]))
+    return out
+
+
+def concat_drop_backward(dx, H, keep: float = 1.0, seeds=None):
+    """cg_concat_drop_backward: dx [N, M, sum H] split into the branches' dh_b
+    [N, M, H_b] through the masks' backward form."""
+    _check_dev("dx", dx)
+    dx = dx.contiguous()
+    N, M, S = (int(s) for s in dx.shape)
+    if sum(H) != S:
+        raise ValueError(f"concat_drop_backward: dx has {S} channels, the branches {sum(H)}")
+    dhs = [torch.empty((N, M, int(h)), device=dx.device, dtype=torch.float32) for h in H]
+    _, _, B, _, Hc, sc = _concat_args(dhs, keep, seeds)
+    _lib.call("cg_concat_drop_backward", B, N, M, Hc, _p(dx), float(keep), sc, _ptr_array(dhs),
+              _stream(dx))
+    return dhs
+
+
+class _ConcatDrop(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, keep, seeds, *hs):
+        out = concat_drop_forward(hs, keep, seeds)
+        ctx.keep, ctx.seeds, ctx.H = keep, seeds, [int(t.shape[-1]) for t in hs]
+        return out
+
+    @staticmethod
+    def backward(ctx, dx):
+        return (None, None, *concat_drop_backward(dx, ctx.H, ctx.keep, ctx.seeds))
+
+
+def concat_drop(hs, keep: float = 1.0, seeds=None):
+    """tf.concat(hs, axis=2) of the branches' h_T [N, M, H_b] (lib/gconv_lstm.py
+    :451, :590), each branch through its own DropoutWrapper mask (keep, seed_b)
+    on the way: the values of ``torch.cat([dropout(h_b, keep, seed_b)])`` bit
+    for bit, without the dropped tensors and the concat copy.  seed_b is the
+    folded seed (``seed + DROP_WEYL * offset``); keep == 1 is a plain concat."""
+    return _ConcatDrop.apply(float(keep), None if seeds is None else tuple(int(s) for s in seeds), *hs)

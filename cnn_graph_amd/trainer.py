@@ -1,5 +1,5 @@
-"""``FlatTrainer``: what the four device models (``ResGNN``, ``StackedResGNN``,
-``GLSTMModel``, ``GLSTMGconvModel``) share around their forward and backward
+"""``FlatTrainer``: what the device models (``ResGNN``, ``StackedResGNN``,
+``GLSTMModel``, ``GLSTMGconvModel``, ``GLSTMPeriodModel``) share around their forward and backward
 passes (lib/graph_model.py:246-310; sgd / rmsprop of lib/gconvRNN.py:381-389).
 
   buffers   every parameter is a view into ONE flat fp32 buffer (``flat``),
@@ -87,6 +87,15 @@ class FlatTrainer:
         self._tensors.append(w)
         self._grads.append(g)
         return w, g
+
+    def align(self, floats: int = 4):
+        """Advance the carving offset to the next multiple of ``floats`` (a view
+        a kernel reads as float4 must start 16-byte aligned).  The skipped
+        entries belong to no parameter: they are zero with a zero gradient, and
+        no optimizer moves such an entry."""
+        pad = -self._off % floats
+        self.flat[self._off:self._off + pad].zero_()
+        self._off += pad
 
     def _carved(self):
         assert self._off == self.flat.numel(), (self._off, self.flat.numel())

@@ -638,6 +638,53 @@ int cg_seq_xent_head(const float* hs, const float* w, const float* b, const int3
                      float* db, void* ws, size_t ws_bytes, void* hip_stream);
 
 /* ---------------------------------------------------------------------------
+ * The two seams of the closeness / period / trend gconv-LSTM networks
+ * (lib/gconv_lstm.py:431-607; glstm_period.GLSTMPeriodModel).  Additive to
+ * version 301.  B branches, 1 <= B <= 4; y, w, dy, dw, h, dh, H and seed are
+ * HOST arrays of B entries (device pointers, sizes, seeds), read before the
+ * call returns.
+ *
+ * cg_branch_merge_forward: the merge by learned per-vertex weights (:494-497,
+ *   :528-531), out[n,m,f] = ((y_0 w_0) + y_1 w_1) + ... + y_{B-1} w_{B-1} with
+ *   y_b [N][M][F] and w_b [M][F] broadcast over n.  Every product and every sum
+ *   is rounded to fp32 in that order (no contraction): bit for bit the chain of
+ *   elementwise multiplies and adds the reference graph builds.  No ReLU
+ *   (cg_stack_merge_* has one built in).
+ * cg_branch_merge_backward: ONE launch for all branches, one pass over dout
+ *   and the y_b:  dy_b[n,m,f] = dout[n,m,f] w_b[m,f]  and
+ *   dw_b[m,f] (+)= sum_n dout[n,m,f] y_b[n,m,f]  (accumulate_dw adds into dw_b).
+ *   The batch sum runs inside one workgroup in a fixed order (eight batch lanes
+ *   walk n = r, r + 8, ... ascending, their partials are added r = 0 .. 7), so
+ *   there are no atomics, no workspace, and two calls agree bitwise.  dy / dw
+ *   (the host arrays) or any entry of them may be NULL to skip that output; at
+ *   least one output is required.
+ * cg_concat_drop_forward: out [N][M][sum H_b], branch b's channels at column
+ *   offset sum_{b' < b} H_b', each element through branch b's DropoutWrapper
+ *   mask with the arithmetic of cg_dropout_forward on the flat index inside
+ *   branch b's own [N][M][H_b]; seed_b is already offset as for
+ *   cg_fres_forward_drop.  Bit for bit cat_b(cg_dropout_forward(h_b, seed_b))
+ *   without the dropped tensors and the concat copy; keep == 1 is a plain
+ *   concat.
+ * cg_concat_drop_backward: the split of dx [N][M][sum H_b] into dh_b
+ *   [N][M][H_b] through cg_dropout_backward's arithmetic, bit for bit.
+ *
+ * dwordx4 accesses when the row (M*F; every H_b) is a multiple of four floats
+ * and every pointer of the call is 16-byte aligned, the scalar kernels
+ * otherwise, chosen per call.  Null required pointers, non-positive sizes, B
+ * outside [1, 4], keep outside (0, 1], an output that is one of the inputs and
+ * two outputs in one buffer return CG_ERR_ARG before any device work.
+ * ------------------------------------------------------------------------- */
+int cg_branch_merge_forward(int32_t B, int32_t N, int32_t M, int32_t F, const float* const* y,
+                            const float* const* w, float* out, void* stream);
+int cg_branch_merge_backward(int32_t B, int32_t N, int32_t M, int32_t F, const float* dout,
+                             const float* const* y, const float* const* w, float* const* dy,
+                             float* const* dw, int32_t accumulate_dw, void* stream);
+int cg_concat_drop_forward(int32_t B, int32_t N, int32_t M, const int32_t* H, const float* const* h,
+                           float keep, const uint64_t* seed, float* out, void* stream);
+int cg_concat_drop_backward(int32_t B, int32_t N, int32_t M, const int32_t* H, const float* dx,
+                            float keep, const uint64_t* seed, float* const* dh, void* stream);
+
+/* ---------------------------------------------------------------------------
  * perm_data (lib/coarsening.py:219-240) on device:
  *   out[n][i][f] = perm[i] < M_in ? x[n][perm[i]][f] : 0   (fake vertices are 0)
  * x [N][M_in][F], perm [M_out] (int32), out [N][M_out][F].

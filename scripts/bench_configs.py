@@ -15,13 +15,18 @@
       K=3, keep 0.8): the fused per-step softmax head against its composition from
       ops.dropout and torch ops, and the training step with each seam
 
+  EP  the closeness / period / trend step (glstm_period.GLSTMPeriodModel) on config E's
+      graph: N=50, T=(3, 3, 3), K=2, at H=128 with fourier_conv and H=32 with cheby_conv,
+      in both merge modes; and the two seams alone against their composition from
+      existing ops
+
 fwd / bwd are HIP-event timings (torch's current stream, where every C-ABI
 call is enqueued) of one chebyshev5 forward and backward (dx + dW), median of
 rounds; alg_GBps uses SURVEY.md §8d's algorithmic bytes.  Each line carries a
 `cpu_baseline`: the oracle's fwd+bwd of the same config on the host cores
 (bench.py's CPU legs -- the only place outside tests/ that runs oracle/),
 median of the timed passes, with the sub-batch and pass count stated.
-Usage: python scripts/bench_configs.py [A C1 C2 D E EF R RF S] [--d-batch N] [--layout auto|rows|planes]
+Usage: python scripts/bench_configs.py [A C1 C2 D E EF EP R RF S] [--d-batch N] [--layout auto|rows|planes]
                                        [--no-cpu] [--cpu-seconds S]
 """
 from __future__ import annotations
@@ -390,6 +395,91 @@ def glstm_gconv_config(dev, filter="fourier_conv", T=6, N=50, Fin=2, H=128, C=32
     return out
 
 
+def period_config(dev, N=50, T=(3, 3, 3), Fin=2, K=2, keep=0.8, runs=5):
+    """EP: (a) one GLSTMPeriodModel training step on config E's graph at the
+    driver's width (H = 128, fourier_conv) and at H = 32 with cheby_conv, merge by
+    weights (inference_glstm_period_expand) and by concat (..._expand_gconv3);
+    (b) the two seams alone, forward + backward, against their composition from
+    existing ops: torch mul / add plus one sum over n for the merge at [N, M, 2],
+    ops.dropout x B plus torch.cat (and its autograd) for the concat at H per
+    branch.  HIP events, the variants interleaved run by run; per-run numbers,
+    medians and the composition's range."""
+    from cnn_graph_amd.glstm_period import GLSTMPeriodModel
+    _, L = graph_e()
+    M, B = L.shape[0], len(T)
+    g = torch.Generator(device=dev)
+    g.manual_seed(8)
+    modes = {"weights": "inference_glstm_period_expand", "concat": "inference_glstm_period_expand_gconv3"}
+    x = 0.5 * torch.randn((N, M, Fin * sum(T)), device=dev, generator=g)
+    labels = torch.randn((N, M, 2), device=dev, generator=g)
+    models = {f"{filt}_H{H}_{mode}": GLSTMPeriodModel(L, N, T, Fin, num_hidden=H, K=K, layer_count=1,
+                                                      conv_layer_num=1, keep_prob=keep, filter=filt,
+                                                      infer_func=fn, device=dev)
+              for filt, H in (("fourier_conv", 128), ("cheby_conv", 32)) for mode, fn in modes.items()}
+    for m in models.values():
+        for _ in range(3):
+            m.train_step(x, labels)
+    torch.cuda.synchronize()
+    step = {k: [] for k in models}
+    for _ in range(runs):
+        for k, m in models.items():
+            step[k].append(round(ev_ms(lambda: m.train_step(x, labels), 5), 4))
+    out = {"config": "EP", "M": M, "N": N, "T": list(T), "Fin": Fin, "K": K, "keep_prob": keep,
+           "step_runs_ms": step,
+           "step_median_ms": {k: round(float(np.median(v)), 4) for k, v in step.items()}}
+
+    # -- the seams alone ---------------------------------------------------------------------
+    F = 2
+    ys = [torch.randn((N, M, F), device=dev, generator=g) for _ in range(B)]
+    ws = [torch.randn((M, F), device=dev, generator=g) for _ in range(B)]
+    dout = torch.randn((N, M, F), device=dev, generator=g)
+
+    def merge_kernel():
+        ops.branch_merge_forward(ys, ws)
+        return ops.branch_merge_backward(dout, ys, ws)
+
+    def merge_composed():
+        acc = ys[0] * ws[0]
+        for y, w in zip(ys[1:], ws[1:]):
+            acc = acc + y * w
+        return [dout * w for w in ws], [(dout * y).sum(0) for y in ys]
+
+    seeds = [11, 22, 33, 44][:B]
+    seam = {}
+    for H in (128, 32):
+        hs = [torch.randn((N, M, H), device=dev, generator=g) for _ in range(B)]
+        dx = torch.randn((N, M, B * H), device=dev, generator=g)
+
+        def concat_kernel():
+            ops.concat_drop_forward(hs, keep, seeds)
+            return ops.concat_drop_backward(dx, [H] * B, keep, seeds)
+
+        def concat_composed():
+            leaves = [h.detach().requires_grad_() for h in hs]
+            torch.cat([ops.dropout(h, keep, s) for h, s in zip(leaves, seeds)], dim=2).backward(dx)
+            return [h.grad for h in leaves]
+
+        pairs = {f"concat_H{H}": (concat_kernel, concat_composed)}
+        if H == 128:
+            pairs["merge"] = (merge_kernel, merge_composed)
+        for name, (kern, comp) in pairs.items():
+            for _ in range(3):
+                kern(), comp()
+            r = {"kernel": [], "composed": []}
+            for _ in range(runs):
+                r["kernel"].append(round(ev_ms(kern, 20), 4))
+                r["composed"].append(round(ev_ms(comp, 20), 4))
+            seam[name] = {"runs_ms": r, "median_ms": {k: round(float(np.median(v)), 4) for k, v in r.items()},
+                          "composed_range_ms": [min(r["composed"]), max(r["composed"])],
+                          "kernel_range_ms": [min(r["kernel"]), max(r["kernel"])]}
+    out["seams_fwd_bwd"] = seam
+    # bytes one kernel pass moves: merge fwd reads B y + B w, writes out; bwd reads dout, B y, B w,
+    # writes B dy + B dw.  concat fwd / bwd: read and write the B branches once each
+    out["merge_alg_bytes"] = 4 * ((B + 1) * N * M * F + B * M * F) + 4 * ((2 * B + 1) * N * M * F + 2 * B * M * F)
+    out["concat_alg_bytes"] = {f"H{H}": 4 * 4 * B * N * M * H for H in (128, 32)}
+    return out
+
+
 def seq_head_config(dev, T=12, N=128, Fin=2, H=32, K=3, keep=0.8, runs=5):
     """S: the gconvRNN sequence model (gconv_rnn.GConvRNNModel) at config E's
     graph and shape.  (a) the fused head (cg_seq_xent_head: mask, logits,
@@ -538,6 +628,8 @@ def main():
             out = glstm_gconv_config(dev, filter=args.filter)
         elif name == "S":
             out = seq_head_config(dev)
+        elif name == "EP":
+            out = period_config(dev)
         elif name == "R":
             out = resgnn_config(dev)
             cpu = lambda: bench.cpu_baseline_resgnn(graph_e()[1], 2, 100, 2, 32, 20, 4,  # noqa: E731
