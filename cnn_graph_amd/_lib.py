@@ -164,6 +164,7 @@ _SIGNATURES = {
     "cg_lstm_bwd_step": ([_vp, _c_i32, _c_i32, _c_i32, _c_i32, _vp, _vp, _vp, _vp, _c_i32, _vp,
                           _vp, _vp, _vp, _vp, _vp, _vp], _c_int),
     "cg_perm_gather": ([_vp, _vp, _c_i32, _c_i32, _c_i32, _c_i32, _vp, _vp], _c_int),
+    "cg_batch_gather": ([_vp, _vp, _vp, _c_i32, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp], _c_int),
     "cg_maxpool_forward": ([_vp, _c_i32, _c_i32, _c_i32, _c_i32, _vp, _vp, _vp], _c_int),
     "cg_maxpool_backward": ([_vp, _vp, _c_i32, _c_i32, _c_i32, _c_i32, _vp, _vp], _c_int),
     "cg_avgpool_forward": ([_vp, _c_i32, _c_i32, _c_i32, _c_i32, _vp, _vp], _c_int),

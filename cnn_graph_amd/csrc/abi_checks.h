@@ -1,5 +1,5 @@
 // Argument checks and workspace sizes shared by the C-ABI files (cheb_abi.cpp,
-// fourier_abi.cpp): host code only, no kernel includes this.
+// fourier_abi.cpp, train_abi.cpp): host code only, no kernel includes this.
 #pragma once
 
 #include <algorithm>
@@ -42,6 +42,14 @@ inline int all_distinct(const char* what, std::initializer_list<const void*> buf
     for (auto b = a + 1; b != bufs.end(); ++b)
       if (*a && *a == *b) return fail(CG_ERR_ARG, "%s must be distinct buffers", what);
   return CG_OK;
+}
+
+// A tensor of a * b elements (a, b >= 1) that a kernel indexes in 32 bits:
+// a * b < 2^31.  `what` names the entry and the tensor.
+inline int below_2_31(const char* what, int64_t a, int64_t b) {
+  if (a <= INT32_MAX / b) return CG_OK;
+  return fail(CG_ERR_ARG, "%s has %lld x %lld elements, the kernel indexes below 2^31", what,
+              (long long)a, (long long)b);
 }
 
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }

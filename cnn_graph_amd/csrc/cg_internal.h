@@ -577,6 +577,11 @@ hipError_t launch_fmix(int form, int64_t R, int M, int Cin, int Cout, const floa
 // ---- misc ----------------------------------------------------------------------
 hipError_t launch_perm_gather(const float* x, const int32_t* perm, int N, int M_in, int M_out,
                               int F, float* out, hipStream_t s);
+// float4 lanes when row % 4 == 0, lrow % 4 == 0 and every pointer is 16-byte
+// aligned, scalar lanes otherwise; labels / y NULL: data only
+hipError_t launch_batch_gather(const float* data, const float* labels, const int32_t* idx, int N,
+                               int64_t S, int64_t row, int64_t lrow, float* x, float* y,
+                               hipStream_t s);
 hipError_t launch_maxpool_fwd(const float* x, int N, int M, int F, int p, float* y, int32_t* arg,
                               hipStream_t s);
 hipError_t launch_maxpool_bwd(const float* dy, const int32_t* arg, int N, int M, int F, int p,

@@ -1,11 +1,13 @@
 // Ops either side of the Chebyshev filter on gfx950:
 //   perm_gather  -- lib/coarsening.py:219-240 perm_data (fake vertices -> 0)
+//   batch_gather -- lib/graph_model.py:149 train_data[idx, :], train_labels[idx] (dataset on device)
 //   maxpool      -- lib/graph_conv.py:201-209 mpool1 (+ first-max argmax, scatter-free grad)
 //   avgpool      -- lib/graph_conv.py:211-218 apool1
 //   adam         -- lib/graph_model.py:293-298 (TF-1.x AdamOptimizer update rule)
 // All are HBM-streaming, one thread per output element, F (the feature axis,
 // contiguous in memory) on consecutive lanes so loads and stores coalesce.
 #include "cg_internal.h"
+#include "launch.h"
 
 namespace cg {
 namespace {
@@ -29,6 +31,44 @@ __global__ __launch_bounds__(256) void k_perm_gather(const float* __restrict__ x
     const int64_t v = t % M_out, n = t / M_out;
     const int src = perm[v];
     out[i] = (src >= 0 && src < M_in) ? x[(n * M_in + src) * F + f] : 0.f;
+  }
+}
+
+template <typename V>
+__device__ __forceinline__ V zero_of();
+template <>
+__device__ __forceinline__ float zero_of<float>() {
+  return 0.f;
+}
+template <>
+__device__ __forceinline__ float4 zero_of<float4>() {
+  return make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// One training batch out of a device-resident dataset (the train_data[idx, :],
+// train_labels[idx] of lib/graph_model.py:149), data and labels in one launch:
+//   x[n] = data[idx[n]], y[n] = labels[idx[n]], a zero row for idx[n] outside [0, S).
+// V is float4 or float; row, lrow, nx = N row and total = N (row + lrow) count
+// V's.  N row and N lrow are each below 2^31 (the entry checks it), so an
+// output offset and its division run in 32 bits; the source offset
+// idx[n] * row is 64-bit.  idx is
+// read at n < N only, and a source row only after its index passed the range
+// test: no index value makes the kernel touch memory outside its arguments.
+template <typename V>
+__global__ __launch_bounds__(256) void k_batch_gather(const V* __restrict__ data,
+                                                      const V* __restrict__ labels,
+                                                      const int32_t* __restrict__ idx, int64_t S,
+                                                      uint32_t row, uint32_t lrow, uint32_t nx,
+                                                      uint32_t total, V* __restrict__ x,
+                                                      V* __restrict__ y) {
+  for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < total;
+       i += int64_t(gridDim.x) * 256) {
+    const bool lab = i >= nx;
+    const uint32_t j = lab ? uint32_t(i) - nx : uint32_t(i);
+    const uint32_t w = lab ? lrow : row;
+    const uint32_t n = j / w, c = j - n * w;
+    const int64_t src = idx[n];
+    (lab ? y : x)[j] = (src >= 0 && src < S) ? (lab ? labels : data)[src * w + c] : zero_of<V>();
   }
 }
 
@@ -217,6 +257,29 @@ hipError_t launch_perm_gather(const float* x, const int32_t* perm, int N, int M_
   hipLaunchKernelGGL(k_perm_gather, dim3(grid_for(total, 256)), dim3(256), 0, s, x, perm, N, M_in,
                      M_out, F, out);
   return hipGetLastError();
+}
+
+hipError_t launch_batch_gather(const float* data, const float* labels, const int32_t* idx, int N,
+                               int64_t S, int64_t row, int64_t lrow, float* x, float* y,
+                               hipStream_t s) {
+  if (!labels) lrow = 0;
+  const bool v4 = row % 4 == 0 && lrow % 4 == 0 &&
+                  ((reinterpret_cast<uintptr_t>(data) | reinterpret_cast<uintptr_t>(labels) |
+                    reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0;
+  const int per = v4 ? 4 : 1;
+  const uint32_t r = uint32_t(row / per), l = uint32_t(lrow / per);
+  const uint32_t nx = uint32_t(N) * r, total = nx + uint32_t(N) * l;
+  // sized from the elements, not from N (one long row still fills the device);
+  // past eight workgroups a CU the grid-stride loop takes the rest
+  const int cus = device_cus(current_device());
+  const int64_t cap = int64_t(cus > 0 ? cus : 256) * 8;
+  const int64_t want = (int64_t(total) + 255) / 256;
+  const dim3 grid(unsigned(want < cap ? want : cap)), block(256);
+  if (v4)
+    return launch(k_batch_gather<float4>, grid, block, 0, s, reinterpret_cast<const float4*>(data),
+                  reinterpret_cast<const float4*>(labels), idx, S, r, l, nx, total,
+                  reinterpret_cast<float4*>(x), reinterpret_cast<float4*>(y));
+  return launch(k_batch_gather<float>, grid, block, 0, s, data, labels, idx, S, r, l, nx, total, x, y);
 }
 
 hipError_t launch_maxpool_fwd(const float* x, int N, int M, int F, int p, float* y, int32_t* arg,

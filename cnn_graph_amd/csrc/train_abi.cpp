@@ -1,6 +1,6 @@
 // C ABI of the training ops (see include/cheb_mi355.h): loss, dropout, clip,
 // seq_xent, slice and stack, weight and bias gradients, bias_act, gemm, pooling,
-// perm and the optimizers -- argument validation and the launches.
+// perm, the batch gather and the optimizers -- argument validation and the launches.
 #include "../../include/cheb_mi355.h"
 
 #include <hip/hip_runtime.h>
@@ -234,6 +234,25 @@ int cg_perm_gather(const float* x, const int32_t* perm, int32_t N, int32_t M_in,
     return fail(CG_ERR_ARG, "perm_gather: bad arguments");
   CG_HIP(cg::launch_perm_gather(x, perm, N, M_in, M_out, F, out,
                                 reinterpret_cast<hipStream_t>(stream)));
+  return ok();
+}
+
+int cg_batch_gather(const float* data, const float* labels, const int32_t* idx, int32_t N, int64_t S,
+                    int64_t row, int64_t lrow, float* x, float* y, void* stream) {
+  if (!data || !idx || !x) return fail(CG_ERR_ARG, "batch_gather: null data / idx / x");
+  if (N < 1 || S < 1 || row < 1)
+    return fail(CG_ERR_ARG, "batch_gather: bad sizes (N=%d S=%lld row=%lld)", N, (long long)S,
+                (long long)row);
+  if (!labels != !y)
+    return fail(CG_ERR_ARG, "batch_gather: labels and y go together (both or neither)");
+  if (labels && lrow < 1) return fail(CG_ERR_ARG, "batch_gather: lrow = %lld", (long long)lrow);
+  if (int rc = cg::below_2_31("batch_gather: x", N, row)) return rc;
+  if (labels)
+    if (int rc = cg::below_2_31("batch_gather: y", N, lrow)) return rc;
+  if (int rc = cg::no_alias("batch_gather: x / y", {x, y}, {data, labels})) return rc;
+  if (int rc = cg::all_distinct("batch_gather: x / y", {x, y})) return rc;
+  CG_HIP(cg::launch_batch_gather(data, labels, idx, N, S, row, lrow, x, y,
+                                 reinterpret_cast<hipStream_t>(stream)));
   return ok();
 }
 

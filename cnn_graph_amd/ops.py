@@ -13,6 +13,7 @@ or a missing library raises.
                                    residual add and ReLU in the synthesis' store
   mpool1, apool1                -- lib/graph_conv.py:201-218
   perm_data                     -- lib/coarsening.py:219-240 (device gather)
+  batch_gather                  -- lib/graph_model.py:149 (a batch out of a dataset on the device)
   adam_update                   -- lib/graph_model.py:293-298
 """
 from __future__ import annotations
@@ -504,6 +505,38 @@ def perm_data(x: torch.Tensor, perm) -> torch.Tensor:
     out = torch.empty((N, Mo, F), device=x.device, dtype=torch.float32)
     _lib.call("cg_perm_gather", _p(x3), _p(perm_t), N, M, Mo, F, _p(out), _stream(x))
     return out[..., 0] if squeeze else out
+
+
+def batch_gather(data: torch.Tensor, labels: torch.Tensor | None, idx: torch.Tensor, N: int,
+                 out_x: torch.Tensor | None = None, out_y: torch.Tensor | None = None):
+    """One training batch out of a dataset on the device (cg_batch_gather; the
+    ``train_data[idx, :], train_labels[idx]`` of lib/graph_model.py:149): ``x[n] =
+    data[idx[n]]``, ``y[n] = labels[idx[n]]`` for n < N in ONE launch, a zero row
+    where ``idx[n]`` is outside [0, S).  data [S, ...] and labels [S, ...] (or
+    None) are contiguous fp32; ``idx`` is an int32 cuda tensor whose first N
+    entries are read.  Returns ``(x, y)`` (``y`` None without labels).  No
+    autograd: the inputs are data."""
+    _check_dev("data", data)
+    _check_dev("idx", idx, torch.int32)
+    N, S = int(N), int(data.shape[0]) if data.dim() else 0
+    if N < 1 or S < 1 or not data.is_contiguous():
+        raise ValueError("batch_gather: data must be a contiguous [S, ...] tensor, S >= 1 and N >= 1")
+    if idx.dim() != 1 or not idx.is_contiguous() or idx.numel() < N:
+        raise ValueError(f"batch_gather: idx must be a contiguous 1-D tensor of at least N = {N} entries")
+    row = data.numel() // S
+    x = _out("out_x", out_x, (N,) + tuple(data.shape[1:]), data.device)
+    y, lrow = None, 0
+    if labels is not None:
+        _check_dev("labels", labels)
+        if labels.dim() < 1 or int(labels.shape[0]) != S or not labels.is_contiguous():
+            raise ValueError(f"batch_gather: labels must be a contiguous [S = {S}, ...] tensor")
+        lrow = labels.numel() // S
+        y = _out("out_y", out_y, (N,) + tuple(labels.shape[1:]), data.device)
+    elif out_y is not None:
+        raise ValueError("batch_gather: out_y without labels")
+    _lib.call("cg_batch_gather", _p(data), _p(labels), _p(idx), N, S, row, lrow, _p(x), _p(y),
+              _stream(data))
+    return x, y
 
 
 def weight_grad(basis: torch.Tensor, dy: torch.Tensor, out: torch.Tensor | None = None,

@@ -13,6 +13,9 @@ passes (lib/graph_model.py:246-310; sgd / rmsprop of lib/gconvRNN.py:381-389).
             (``_grad_scale``), at the staircase exponentially decayed learning
             rate; ``_after_exchange`` runs between exchange and update
   predict / evaluate  GraphModel's (lib/graph_model.py:64-122) through evaluate.py
+  fit       GraphModel.fit (lib/graph_model.py:124-197): the dataset lives on the
+            device, ``fit_schedule`` restates the reference's index deque on the
+            host, and each step is ONE cg_batch_gather plus ``train_step``
 
 A model derives from it, allocates with ``FlatTrainer.__init__``, carves its
 parameters, calls ``_carved()`` and implements ``forward``.  ``comm`` is any
@@ -23,7 +26,9 @@ from __future__ import annotations
 
 import ctypes
 import math
+import time
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -31,6 +36,38 @@ from . import evaluate as _ev
 from . import ops
 
 OPTIMIZERS = ("adam", "sgd", "rmsprop")
+
+
+def fit_schedule(S: int, batch: int, num_steps: int, rng=None) -> np.ndarray:
+    """The sample indices of ``num_steps`` batches of ``batch`` out of ``S``
+    samples, int32 [num_steps, batch], drawn as GraphModel.fit draws them
+    (lib/graph_model.py:139-147): a queue that is refilled with
+    ``permutation(S)`` whenever fewer than ``batch`` indices are left, and a batch
+    is its first ``batch`` entries.  Leftovers carry into the next epoch, so a
+    batch that straddles a refill can hold one sample twice (the reference's
+    behaviour, kept).
+
+    ``rng``: a ``numpy.random.RandomState``; an int seed (``RandomState(seed)``);
+    or None for the global ``numpy.random`` state, which is what the reference
+    draws from -- after ``numpy.random.seed(k)`` the batches are the
+    reference's, in its order."""
+    S, batch, num_steps = int(S), int(batch), int(num_steps)
+    if batch < 1 or num_steps < 0:
+        raise ValueError(f"fit_schedule: batch = {batch}, num_steps = {num_steps}")
+    if S < batch:
+        raise ValueError(f"fit_schedule: {S} samples cannot fill a batch of {batch} (one refill per "
+                         "batch: the reference's popleft raises IndexError here)")
+    if rng is None:
+        rng = np.random
+    elif not isinstance(rng, np.random.RandomState):
+        rng = np.random.RandomState(rng)
+    out = np.empty((num_steps, batch), np.int32)
+    left = np.empty((0,), np.int64)  # the deque, front first
+    for step in range(num_steps):
+        if left.size < batch:
+            left = np.concatenate([left, rng.permutation(S)])
+        out[step], left = left[:batch], left[batch:]
+    return out
 
 
 class FlatTrainer:
@@ -190,3 +227,90 @@ class FlatTrainer:
     def evaluate(self, data, labels, **forward_kw):
         """GraphModel.evaluate (:96-122): (string, mse, 0, loss, predictions)."""
         return _ev.evaluate(lambda d, l: FlatTrainer.predict(self, d, l, **forward_kw), data, labels)
+
+    # -- training -------------------------------------------------------------------
+    def fit(self, train_data, train_labels, val_data, val_labels, num_epochs=20, eval_frequency=200,
+            rng=None, verbose=True, stream=None, rank=None):
+        """GraphModel.fit (lib/graph_model.py:124-197): ``int(num_epochs * S / B)``
+        optimizer steps over shuffled batches (``fit_schedule``), ``evaluate`` on the
+        validation set every ``eval_frequency`` steps and after the last one.
+        Returns ``(accuracies, losses, t_step)``: evaluate's mse and loss at each
+        evaluation, and the wall time per step, evaluations included (:196).
+
+        The four arrays are moved to the device as fp32 once (data [S, M, C],
+        labels with S * M * Fout elements); a dataset that does not fit in device
+        memory next to the model is out of scope.  The whole index schedule is
+        uploaded once as well, so a step is ONE cg_batch_gather into two buffers
+        allocated here and then ``train_step`` on them, in stream order: no host
+        synchronisation between evaluations and no torch indexing.  ``stream`` is
+        ``train_step``'s.
+
+        Data parallel (``comm.world`` > 1): B = N * world is the global batch,
+        every rank builds the same schedule and rank r trains on its columns
+        [r N, (r + 1) N) -- ``dist.shard``'s split.  ``rank`` defaults to the
+        launcher's (``dist.env_rank_world``); ``rng`` must be a seed or a
+        RandomState that is the same on every rank, so None is refused.
+
+        ``verbose`` prints the reference's progress lines (:169-175, :192); the
+        learning rate shown is the one the last step applied.  Checkpoints are
+        not written."""
+        N, M, Fout = (int(v) for v in self.dout.shape)
+        world = self.world
+        if world > 1 and rng is None:
+            raise ValueError("fit: rng=None draws from this process's global numpy state; with "
+                             f"world = {world} every rank must draw the same permutations: pass a seed")
+        if rank is None:
+            rank = 0
+            if self.comm is not None:
+                from . import dist
+                rank = dist.env_rank_world()[0]
+        if not 0 <= int(rank) < world:
+            raise ValueError(f"fit: rank {rank} outside [0, {world})")
+        f32 = dict(device=self.device, dtype=torch.float32)
+        sets = []
+        for name, d, l in (("train", train_data, train_labels), ("val", val_data, val_labels)):
+            d = torch.as_tensor(d).to(**f32).contiguous()
+            l = torch.as_tensor(l).to(**f32).contiguous()
+            if d.dim() != 3 or int(d.shape[1]) != M:
+                raise ValueError(f"fit: {name}_data must be [samples, M = {M}, channels], got {tuple(d.shape)}")
+            if int(l.shape[0]) != int(d.shape[0]):
+                raise ValueError(f"fit: {name} data and labels differ in their number of samples")
+            if l.numel() != int(d.shape[0]) * M * Fout:
+                raise ValueError(f"fit: {name}_labels must hold [samples, {M}, {Fout}] values")
+            sets.append((d, l))
+        (data, labels), (val_data, val_labels) = sets
+        S, B = int(data.shape[0]), N * world
+        num_steps = int(num_epochs * S / B)
+        sched = fit_schedule(S, B, num_steps, rng)  # refuses S < B
+        if num_steps < 1:
+            raise ValueError(f"fit: num_epochs = {num_epochs} over {S} samples is less than one batch of {B}")
+        labels = labels.view(S, M * Fout)
+        row, lrow = data.numel() // S, M * Fout
+        idx = torch.from_numpy(sched).to(self.device)
+        x_b = torch.empty((N,) + tuple(data.shape[1:]), **f32)
+        y_b = torch.empty((N, M, Fout), **f32)
+        s = self._stream(stream)
+        gather = _lib.lib().cg_batch_gather
+        dp, lp, xp, yp = data.data_ptr(), labels.data_ptr(), x_b.data_ptr(), y_b.data_ptr()
+        ip = idx.data_ptr() + 4 * int(rank) * N  # this rank's columns of step 0
+        accuracies, losses = [], []
+        t_process, t_wall = time.process_time(), time.time()
+        for step in range(1, num_steps + 1):
+            _lib.check("cg_batch_gather", gather(dp, lp, ip + 4 * B * (step - 1), N, S, row, lrow, xp, yp, s))
+            self.train_step(x_b, y_b, stream)
+            if step % eval_frequency == 0 or step == num_steps:
+                string, mse, _, loss, _ = self.evaluate(val_data, val_labels)
+                accuracies.append(mse)
+                losses.append(loss)
+                if verbose:
+                    print("step {} / {} (epoch {:.2f} / {}):".format(step, num_steps, step * B / S, num_epochs))
+                    print("  learning_rate = {:.2e}, loss_average = {:.2e}".format(
+                        self.learning_rate(self.step_count - 1), float(self.loss_average)))
+                    print("  validation {}".format(string))
+                    print("  time: {:.0f}s (wall {:.0f}s)".format(time.process_time() - t_process,
+                                                                 time.time() - t_wall))
+        torch.cuda.synchronize(self.device)
+        if verbose:
+            print("validation accuracy: peak = {:.2f}, mean = {:.2f}".format(max(accuracies),
+                                                                            np.mean(accuracies[-10:])))
+        return accuracies, losses, (time.time() - t_wall) / num_steps

@@ -692,6 +692,26 @@ int cg_concat_drop_backward(int32_t B, int32_t N, int32_t M, const int32_t* H, c
 int cg_perm_gather(const float* x, const int32_t* perm, int32_t N, int32_t M_in, int32_t M_out,
                    int32_t F, float* out, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * One training batch out of a dataset that lives on the device: the
+ * train_data[idx, :], train_labels[idx] of GraphModel.fit (lib/graph_model.py:149)
+ * in ONE launch, with the indices on the device too.
+ *   x[n][0:row]  = 0 <= idx[n] < S ? data  [idx[n]][0:row]  : 0      n < N
+ *   y[n][0:lrow] = 0 <= idx[n] < S ? labels[idx[n]][0:lrow] : 0      (labels / y both NULL: data only)
+ * data [S][row] (row = M*C), labels [S][lrow] (lrow = M*Fout), idx [N] int32,
+ * x [N][row], y [N][lrow].  An index outside [0, S) writes a zero row and reads
+ * nothing, so no index value the host never saw reaches memory outside the
+ * arguments, and -1 pads a ragged last batch.  Source offsets are 64-bit
+ * (S*row may pass 2^31); N*row and N*lrow must stay below 2^31.  float4
+ * accesses when row % 4 == 0, lrow % 4 == 0 and all four pointers are 16-byte
+ * aligned, scalar ones otherwise, chosen per call.  CG_ERR_ARG before any
+ * device work: null data / idx / x; N, S or row < 1; labels without y or y
+ * without labels; lrow < 1 with labels; N*row or N*lrow >= 2^31; x or y being
+ * data or labels, x being y.
+ * ------------------------------------------------------------------------- */
+int cg_batch_gather(const float* data, const float* labels, const int32_t* idx, int32_t N, int64_t S,
+                    int64_t row, int64_t lrow, float* x, float* y, void* stream);
+
 /* mpool1 (lib/graph_conv.py:201-209): window = stride = p along vertices,
  * y [N][M/p][F]; argmax [N][M/p][F] = absolute vertex index of the FIRST
  * maximum in window order (TF-1.x CPU MaxPoolGrad tie rule). M % p == 0. */

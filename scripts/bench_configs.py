@@ -20,13 +20,19 @@
       in both merge modes; and the two seams alone against their composition from
       existing ops
 
+  FIT the training loop around a step: ResGNN at config R's shape and GLSTMModel at config
+      E's model step, 2 048 synthetic samples on the device -- (a) train_step on one static
+      batch (the floor), (b) the loop a user writes without fit, train_step(data[i],
+      labels[i]) with a device index tensor, (c) fit's inner loop (cg_batch_gather +
+      train_step); HIP events over 200 steps, interleaved repeats
+
 fwd / bwd are HIP-event timings (torch's current stream, where every C-ABI
 call is enqueued) of one chebyshev5 forward and backward (dx + dW), median of
 rounds; alg_GBps uses SURVEY.md §8d's algorithmic bytes.  Each line carries a
 `cpu_baseline`: the oracle's fwd+bwd of the same config on the host cores
 (bench.py's CPU legs -- the only place outside tests/ that runs oracle/),
 median of the timed passes, with the sub-batch and pass count stated.
-Usage: python scripts/bench_configs.py [A C1 C2 D E EF EP R RF S] [--d-batch N] [--layout auto|rows|planes]
+Usage: python scripts/bench_configs.py [A C1 C2 D E EF EP FIT R RF S] [--d-batch N] [--layout auto|rows|planes]
                                        [--no-cpu] [--cpu-seconds S]
 """
 from __future__ import annotations
@@ -558,6 +564,78 @@ def seq_head_config(dev, T=12, N=128, Fin=2, H=32, K=3, keep=0.8, runs=5):
     return out
 
 
+def fit_config(dev, samples=2048, steps=200, runs=5):
+    """FIT: what the loop around a training step costs.  Per model, on a
+    synthetic dataset of ``samples`` samples that lives on the device and one
+    seeded fit_schedule: (a) ``train_step`` on one static batch, the floor;
+    (b) the loop a user writes without ``fit``, ``train_step(data[i], labels[i])``
+    with i a device index tensor per step (made before the timed window);
+    (c) ``fit``'s inner loop, one cg_batch_gather from the uploaded schedule
+    into two fixed buffers and ``train_step`` on them.  HIP events around
+    ``steps`` steps, the three loops interleaved run by run; per-run numbers,
+    medians and ranges, per step."""
+    from cnn_graph_amd import _lib
+    from cnn_graph_amd.gconv_lstm import GLSTMModel
+    from cnn_graph_amd.model import ResGNN
+    from cnn_graph_amd.trainer import fit_schedule
+    _, L = graph_e()
+    M = L.shape[0]
+    g = torch.Generator(device=dev)
+    g.manual_seed(9)
+    gather = _lib.lib().cg_batch_gather
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    out = {"config": "FIT", "M": M, "samples": samples, "steps_per_run": steps, "runs": runs, "models": {}}
+    builds = {
+        "R_ResGNN": (100, 2, lambda: ResGNN(L, N=100, Fin=2, nfilter=32, K=20, nres_layer_count=4, device=dev)),
+        "E_GLSTMModel": (128, 24, lambda: GLSTMModel(L, 128, T=12, feat_in=2, num_hidden=32, K=3, device=dev)),
+    }
+    for name, (N, C, build) in builds.items():
+        model = build()
+        data = 0.5 * torch.randn((samples, M, C), device=dev, generator=g)
+        labels = torch.randn((samples, M * 2), device=dev, generator=g)
+        sched = fit_schedule(samples, N, steps, 9)
+        idx32 = torch.from_numpy(sched).to(dev)
+        idx64 = [row for row in idx32.long()]  # one device index tensor per step
+        x_b = torch.empty((N, M, C), device=dev)
+        y_b = torch.empty((N, M, 2), device=dev)
+        x0, y0 = data[:N].clone(), labels[:N].view(N, M, 2).clone()
+        lab3 = labels.view(samples, M, 2)
+        dp, lp, ip, xp, yp = (t.data_ptr() for t in (data, labels, idx32, x_b, y_b))
+        row, lrow = M * C, M * 2
+
+        def static():
+            for _ in range(steps):
+                model.train_step(x0, y0)
+
+        def indexed():
+            for i in idx64:
+                model.train_step(data[i], lab3[i])
+
+        def gathered():
+            for k in range(steps):
+                _lib.check("cg_batch_gather", gather(dp, lp, ip + 4 * N * k, N, samples, row, lrow, xp, yp, stream))
+                model.train_step(x_b, y_b)
+
+        loops = {"a_static_batch": static, "b_torch_indexing": indexed, "c_fit_gather": gathered}
+        for fn in loops.values():  # warm every shape the timed windows use
+            fn()
+        torch.cuda.synchronize()
+        per_run = {k: [] for k in loops}
+        for _ in range(runs):
+            for k, fn in loops.items():  # interleaved: drift hits all alike
+                per_run[k].append(round(ev_ms(fn, 1, rounds=1) / steps * 1e3, 2))
+        med = {k: round(float(np.median(v)), 2) for k, v in per_run.items()}
+        rng = {k: [min(v), max(v)] for k, v in per_run.items()}
+        out["models"][name] = {
+            "N": N, "C": C, "batch_bytes": 4 * N * (row + lrow), "step_runs_us": per_run,
+            "step_median_us": med, "step_range_us": rng,
+            "c_minus_a_us": round(med["c_fit_gather"] - med["a_static_batch"], 2),
+            "b_minus_a_us": round(med["b_torch_indexing"] - med["a_static_batch"], 2),
+            "c_below_b_range": bool(rng["c_fit_gather"][1] < rng["b_torch_indexing"][0])}
+        del model, data, labels
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("configs", nargs="*", default=["C1", "C2", "D", "E"])
@@ -630,6 +708,8 @@ def main():
             out = seq_head_config(dev)
         elif name == "EP":
             out = period_config(dev)
+        elif name == "FIT":
+            out = fit_config(dev)
         elif name == "R":
             out = resgnn_config(dev)
             cpu = lambda: bench.cpu_baseline_resgnn(graph_e()[1], 2, 100, 2, 32, 20, 4,  # noqa: E731
