@@ -326,8 +326,11 @@ def test_seq_x_basis_prepass_modes_bitwise(dev, cg_opts, Fin, K, gname):
     recurrence), the states to fp32 rounding (the in-loop build contracts x in
     another MFMA order than the late x contraction of the pre-pass builds).
     Graphs: E (M = 1024: every lane of the pre-pass's 1024-thread workgroup
-    owns a row), B (M = 976, not a multiple of 64) and A (M = 100): lanes past
-    the last row must not touch the LDS copy of the basis."""
+    owns a row) and B (M = 976, not a multiple of 64): lanes past the last row
+    must not touch the LDS copy of the basis.  Graph A (M = 100)
+    does not reach the pre-pass: its longest row has 21 entries, past the 16
+    k_xbasis keeps per thread, so mode 1 runs mode 2's streaming launches there
+    (tests/test_gpu_resident_geometry.py has the pre-pass at M = 100)."""
     from cnn_graph_amd import ops
     from cnn_graph_amd.plan import ChebPlan
     Lt, _, M = graph_E(gname)
