@@ -15,10 +15,12 @@ Modules
   coarsening  graph coarsening + perm_data (lib/coarsening.py API)
   dist        one-process-per-GPU data parallelism (RCCL all-reduce)
   glstm_period  GLSTMPeriodModel: the closeness / period / trend gconv-LSTM networks
+  gconv_net   GConvNetModel: the pure graph-convolution networks (inference_gconv*)
 """
 __version__ = "0.1.0"
 
-__all__ = ["graph", "plan", "ops", "graph_conv", "filter", "coarsening", "dist", "GLSTMPeriodModel"]
+__all__ = ["graph", "plan", "ops", "graph_conv", "filter", "coarsening", "dist", "GLSTMPeriodModel",
+           "GConvNetModel"]
 
 
 def __getattr__(name):
@@ -26,4 +28,7 @@ def __getattr__(name):
     if name == "GLSTMPeriodModel":
         from .glstm_period import GLSTMPeriodModel
         return GLSTMPeriodModel
+    if name == "GConvNetModel":
+        from .gconv_net import GConvNetModel
+        return GConvNetModel
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

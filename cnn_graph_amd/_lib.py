@@ -94,6 +94,7 @@ _SIGNATURES = {
                               _vp, _vp, _c_sz, _vp], _c_int),
     "cg_bias_grad_workspace_bytes": ([_c_i64, _c_i32, ctypes.POINTER(_c_sz)], _c_int),
     "cg_bias_grad": ([_c_i64, _c_i32, _vp, _vp, _c_i32, _vp, _c_sz, _vp], _c_int),
+    "cg_act_forward": ([_c_i64, _vp, _vp, _c_i32, _vp], _c_int),
     "cg_bias_act_forward": ([_c_i64, _c_i32, _vp, _vp, _c_i32, _vp, _vp], _c_int),
     "cg_bias_act_workspace_bytes": ([_c_i64, _c_i32, ctypes.POINTER(_c_sz)], _c_int),
     "cg_bias_act_backward": ([_c_i64, _c_i32, _vp, _vp, _c_i32, _vp, _vp, _c_i32, _vp, _c_sz, _vp],

@@ -773,7 +773,7 @@ int forward_impl(cg_plan* plan, int32_t N, int32_t Fin, int32_t K, int32_t Fout,
   if (rc) return rc;
   if ((rc = check_layout(plan, Fin, K, Fout, layout))) return rc;
   if (!x) return fail(CG_ERR_ARG, "null x");
-  if (act != CG_ACT_NONE && act != CG_ACT_RELU) return fail(CG_ERR_ARG, "unknown activation %d", act);
+  if (act < CG_ACT_NONE || act > CG_ACT_TANH) return fail(CG_ERR_ARG, "unknown activation %d", act);
   if (!y && (res || act)) return fail(CG_ERR_ARG, "an epilogue needs y");
   if (y && !W) return fail(CG_ERR_ARG, "null W with non-null y");
   if (!y && !basis) return fail(CG_ERR_ARG, "nothing to compute (basis and y both null)");
@@ -1101,16 +1101,18 @@ int backward_ex_impl(cg_plan* plan, int32_t N, int32_t Fin, int32_t K, int32_t F
                      const float* dy, const float* y, int32_t act, int layout, const float* basis,
                      const float* W, float* dx, int32_t dx_accumulate, float* dW, float* dz,
                      void* workspace, size_t ws_bytes, void* stream) {
-  if (act != CG_ACT_NONE && act != CG_ACT_RELU) return fail(CG_ERR_ARG, "unknown activation %d", act);
+  if (act < CG_ACT_NONE || act > CG_ACT_TANH) return fail(CG_ERR_ARG, "unknown activation %d", act);
   if (!plan || !dy) return fail(CG_ERR_ARG, "null plan / dy");
   int rc = check_shape(plan, N, Fin, K, Fout);
   if (rc) return rc;
   if ((rc = check_layout(plan, Fin, K, Fout, layout))) return rc;
   const float* dy_eff = dy;
-  if (act == CG_ACT_RELU) {
-    if (!y || !dz) return fail(CG_ERR_ARG, "ReLU backward needs y (its output) and dz");
-    CG_HIP(cg::launch_relu_bwd(dy, y, dz, int64_t(N) * plan->M * Fout,
-                               reinterpret_cast<hipStream_t>(stream)));
+  if (act != CG_ACT_NONE) {
+    if (!y || !dz)
+      return fail(CG_ERR_ARG, "%s backward needs y (its output) and dz",
+                  act == CG_ACT_RELU ? "ReLU" : "tanh");
+    CG_HIP(cg::launch_act_bwd(dy, y, act, dz, int64_t(N) * plan->M * Fout,
+                              reinterpret_cast<hipStream_t>(stream)));
     dy_eff = dz;
   } else if (dz) {
     CG_HIP(hipMemcpyAsync(dz, dy, size_t(N) * plan->M * Fout * sizeof(float),

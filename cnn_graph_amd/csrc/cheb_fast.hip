@@ -6,7 +6,7 @@
 
 namespace cg {
 namespace fastk {
-template <int FV, int NT, bool OB>
+template <int FV, int NT, bool OB, bool TH>
 hipError_t launch_fwd_fast_t(size_t lds, int N, const FastFwdArgs& a, hipStream_t s);
 template <int FV, int DW>
 hipError_t launch_bwd_fast_t(size_t lds, int N, const FastBwdArgs& a, hipStream_t s);
@@ -32,17 +32,25 @@ FastGeom fast_geometry(int M, int P, int max_row_nnz, int max_row_nnzT, int Fin,
   return g;
 }
 
-hipError_t launch_fast_forward(const FastGeom& g, int N, const FastFwdArgs& a, hipStream_t s) {
+namespace {
+// TH: the tanh instantiations (act == 2), apart from the none / ReLU ones
+template <bool TH>
+hipError_t fast_forward_t(const FastGeom& g, int N, const FastFwdArgs& a, hipStream_t s) {
   // orders-layout basis: Fin <= 2 (cheb_abi.cpp::check_layout)
-#define CG_F(FV_, NT_)                                                                   \
-  if (a.Fin == FV_ && g.nt == NT_)                                                       \
-    return a.bord ? fastk::launch_fwd_fast_t<FV_, NT_, true>(g.fwd_lds_ob, N, a, s)      \
-                  : fastk::launch_fwd_fast_t<FV_, NT_, false>(g.fwd_lds, N, a, s);
+#define CG_F(FV_, NT_)                                                                     \
+  if (a.Fin == FV_ && g.nt == NT_)                                                         \
+    return a.bord ? fastk::launch_fwd_fast_t<FV_, NT_, true, TH>(g.fwd_lds_ob, N, a, s)    \
+                  : fastk::launch_fwd_fast_t<FV_, NT_, false, TH>(g.fwd_lds, N, a, s);
   CG_F(1, 1) CG_F(1, 2) CG_F(2, 1) CG_F(2, 2)
 #undef CG_F
-  if (a.Fin == 4 && !a.bord && g.nt == 1) return fastk::launch_fwd_fast_t<4, 1, false>(g.fwd_lds, N, a, s);
-  if (a.Fin == 4 && !a.bord && g.nt == 2) return fastk::launch_fwd_fast_t<4, 2, false>(g.fwd_lds, N, a, s);
+  if (a.Fin == 4 && !a.bord && g.nt == 1) return fastk::launch_fwd_fast_t<4, 1, false, TH>(g.fwd_lds, N, a, s);
+  if (a.Fin == 4 && !a.bord && g.nt == 2) return fastk::launch_fwd_fast_t<4, 2, false, TH>(g.fwd_lds, N, a, s);
   return hipErrorInvalidValue;
+}
+}  // namespace
+
+hipError_t launch_fast_forward(const FastGeom& g, int N, const FastFwdArgs& a, hipStream_t s) {
+  return a.act == 2 ? fast_forward_t<true>(g, N, a, s) : fast_forward_t<false>(g, N, a, s);
 }
 
 hipError_t launch_fast_backward(const FastGeom& g, int N, const FastBwdArgs& a, hipStream_t s) {

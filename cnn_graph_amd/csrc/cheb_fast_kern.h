@@ -50,6 +50,7 @@
 
 #include "cg_internal.h"
 #include "launch.h"
+#include "lstm_gates.h"
 #include "split_bf16.h"
 
 namespace cg {
@@ -445,7 +446,11 @@ struct Fwd {
   }
 };
 
-template <int FV, int NT, bool OB>
+// TH: the y store applies tanh (act == CG_ACT_TANH).  A compile-time variant,
+// chosen by launch_fast_forward, so the none / ReLU instantiations keep their
+// code: ~25 VALU instructions in a store unrolled MT x NT x 16 times would
+// grow kernels that already overrun the instruction cache.
+template <int FV, int NT, bool OB, bool TH>
 __global__ __launch_bounds__(kT) void cheb_fwd_fast(FastFwdArgs A) {
 #pragma clang fp contract(off)
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -486,7 +491,8 @@ __global__ __launch_bounds__(kT) void cheb_fwd_fast(FastFwdArgs A) {
             if (m < M && f < Fout) {
               float v = c.acc[t][q][e];
               if (A.res) v = v + A.res[size_t(n) * M * Fout + size_t(m) * Fout + f];
-              if (A.act) v = v > 0.f ? v : 0.f;
+              if (TH) v = gate_tanh(v);
+              else if (A.act) v = v > 0.f ? v : 0.f;
               yn[size_t(m) * Fout + f] = v;
             }
           }
@@ -1005,9 +1011,9 @@ __global__ __launch_bounds__(kT) void cheb_bwd_fast(FastBwdArgs A) {
   CG_TS(A.ts, 5);
 }
 
-template <int FV, int NT, bool OB>
+template <int FV, int NT, bool OB, bool TH>
 hipError_t launch_fwd_fast_t(size_t lds, int N, const FastFwdArgs& a, hipStream_t s) {
-  return launch_big_lds(&cheb_fwd_fast<FV, NT, OB>, dim3(N), dim3(kT), lds, s, a);
+  return launch_big_lds(&cheb_fwd_fast<FV, NT, OB, TH>, dim3(N), dim3(kT), lds, s, a);
 }
 
 template <int FV, int DW>

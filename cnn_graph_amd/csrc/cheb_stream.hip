@@ -22,6 +22,7 @@
 // the basis is bit-identical to the resident path and to lib/graph.py::chebyshev.
 #include "cg_internal.h"
 #include "launch.h"
+#include "lstm_gates.h"
 #include "split_bf16.h"
 
 #include <algorithm>
@@ -406,7 +407,8 @@ __global__ __launch_bounds__(256) void k_rowgemm(RowGemmArgs a) {
         if (rr < a.R) {
           float v = acc[t][q];
           if (a.res) v = v + a.res[rr * a.ldc + col];
-          if (a.act) v = v > 0.f ? v : 0.f;
+          if (a.act == 2) v = gate_tanh(v);
+          else if (a.act) v = v > 0.f ? v : 0.f;
           Cp[rr * a.ldc + col] = v;
         }
       }
@@ -513,7 +515,8 @@ __global__ __launch_bounds__(256) void k_rowgemm_x3(RowGemmArgs a) {
         if (rr < a.R) {
           float v = acc[t][q];
           if (a.res) v = v + a.res[rr * a.ldc + col];
-          if (a.act) v = v > 0.f ? v : 0.f;
+          if (a.act == 2) v = gate_tanh(v);
+          else if (a.act) v = v > 0.f ? v : 0.f;
           Cp[rr * a.ldc + col] = v;
         }
       }

@@ -1,8 +1,9 @@
 // Elementwise pieces of the residual GraphConv block and its training step
 // (lib/graph_conv.py:234-330, lib/graph_model.py:246-298), for the paths whose
 // contraction kernel does not apply them itself:
-//   k_act_fwd   y = act(y + res)              (b1relu of x + x_identity, :256-262)
-//   k_relu_bwd  dz = y > 0 ? dy : 0           (ReLU gradient from its output)
+//   k_act_fwd   y = act(y + res)              (b1relu of x + x_identity, :256-262;
+//               tanh of lib/gconv_lstm.py:642-658 by cg::gate_tanh)
+//   k_act_bwd   dz = dy * act'(y)             (ReLU / tanh gradient from the output)
 //   k_bias_act_fwd / k_bias_act_bwd
 //               y = act(x + b) with a per-filter (b1*, :189-193) or per-vertex-
 //               and-filter (b2relu, :195-199) bias; dz = dy * act'(y)
@@ -23,8 +24,9 @@
 //               optimizer (lib/gconvRNN.py:392-402): t' = (t * c) / max(||t||, c),
 //               ||t|| from a fixed-order sum of squares, non-finite t' flagged
 // The fast resident forward and the streaming row GEMM apply the residual /
-// ReLU epilogue in their own y store; these kernels are the fallback.
+// ReLU / tanh epilogue in their own y store; these kernels are the fallback.
 #include "cg_internal.h"
+#include "lstm_gates.h"
 
 namespace cg {
 namespace {
@@ -39,7 +41,8 @@ __global__ __launch_bounds__(256) void k_act_fwd(float* __restrict__ y, const fl
   for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n; i += int64_t(gridDim.x) * 256) {
     float v = y[i];
     if (res) v = v + res[i];
-    if (act) v = v > 0.f ? v : 0.f;
+    if (act == 2) v = gate_tanh(v);
+    else if (act) v = v > 0.f ? v : 0.f;
     y[i] = v;
   }
 }
@@ -107,21 +110,28 @@ __global__ __launch_bounds__(1024) void k_clip_norm(float* __restrict__ t, int64
   if (tid == 0 && bad && nonfinite) *nonfinite = 1;
 }
 
-__global__ __launch_bounds__(256) void k_relu_bwd(const float* __restrict__ dy,
-                                                  const float* __restrict__ y,
-                                                  float* __restrict__ dz, int64_t n) {
+// dz = dy * act'(y) from the epilogue's OUTPUT y: ReLU (act 1) y > 0 ? dy : 0,
+// tanh (act 2) dy * (1 - y*y) (TF ReluGrad / TanhGrad, as k_bias_act_bwd)
+__device__ __forceinline__ float act_mask(float g, float v, int act) {
+#pragma clang fp contract(off)
+  return act == 2 ? g * (1.f - v * v) : (v > 0.f ? g : 0.f);
+}
+
+__global__ __launch_bounds__(256) void k_act_bwd(const float* __restrict__ dy,
+                                                 const float* __restrict__ y, int act,
+                                                 float* __restrict__ dz, int64_t n) {
   for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n; i += int64_t(gridDim.x) * 256)
-    dz[i] = y[i] > 0.f ? dy[i] : 0.f;
+    dz[i] = act_mask(dy[i], y[i], act);
 }
 
 // the same, four elements per lane (16-byte aligned operands, n % 4 == 0)
-__global__ __launch_bounds__(256) void k_relu_bwd4(const float4* __restrict__ dy,
-                                                   const float4* __restrict__ y,
-                                                   float4* __restrict__ dz, int64_t n4) {
+__global__ __launch_bounds__(256) void k_act_bwd4(const float4* __restrict__ dy,
+                                                  const float4* __restrict__ y, int act,
+                                                  float4* __restrict__ dz, int64_t n4) {
   for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n4; i += int64_t(gridDim.x) * 256) {
     const float4 g = dy[i], v = y[i];
-    dz[i] = make_float4(v.x > 0.f ? g.x : 0.f, v.y > 0.f ? g.y : 0.f, v.z > 0.f ? g.z : 0.f,
-                        v.w > 0.f ? g.w : 0.f);
+    dz[i] = make_float4(act_mask(g.x, v.x, act), act_mask(g.y, v.y, act), act_mask(g.z, v.z, act),
+                        act_mask(g.w, v.w, act));
   }
 }
 
@@ -276,16 +286,17 @@ hipError_t launch_act_fwd(float* y, const float* res, int act, int64_t n, hipStr
   return hipGetLastError();
 }
 
-hipError_t launch_relu_bwd(const float* dy, const float* y, float* dz, int64_t n, hipStream_t s) {
+hipError_t launch_act_bwd(const float* dy, const float* y, int act, float* dz, int64_t n,
+                          hipStream_t s) {
   const bool a16 = ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(y) |
                      reinterpret_cast<uintptr_t>(dz)) & 15) == 0;
   if (a16 && n % 4 == 0) {
-    hipLaunchKernelGGL(k_relu_bwd4, dim3(grid1d(n / 4, 256)), dim3(256), 0, s,
-                       reinterpret_cast<const float4*>(dy), reinterpret_cast<const float4*>(y),
+    hipLaunchKernelGGL(k_act_bwd4, dim3(grid1d(n / 4, 256)), dim3(256), 0, s,
+                       reinterpret_cast<const float4*>(dy), reinterpret_cast<const float4*>(y), act,
                        reinterpret_cast<float4*>(dz), n / 4);
     return hipGetLastError();
   }
-  hipLaunchKernelGGL(k_relu_bwd, dim3(grid1d(n, 256)), dim3(256), 0, s, dy, y, dz, n);
+  hipLaunchKernelGGL(k_act_bwd, dim3(grid1d(n, 256)), dim3(256), 0, s, dy, y, act, dz, n);
   return hipGetLastError();
 }
 

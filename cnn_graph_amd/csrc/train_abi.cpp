@@ -188,6 +188,14 @@ int cg_bias_act_forward(int64_t n, int32_t bias_len, const float* x, const float
   return ok();
 }
 
+int cg_act_forward(int64_t n, float* y, const float* residual, int32_t act, void* stream) {
+  if (!y || n < 1) return fail(CG_ERR_ARG, "act_forward: bad arguments");
+  if (act < CG_ACT_NONE || act > CG_ACT_TANH) return fail(CG_ERR_ARG, "unknown activation %d", act);
+  if (residual == y) return fail(CG_ERR_ARG, "act_forward: residual aliases y");
+  CG_HIP(cg::launch_act_fwd(y, residual, act, n, reinterpret_cast<hipStream_t>(stream)));
+  return ok();
+}
+
 int cg_bias_act_workspace_bytes(int64_t n, int32_t bias_len, size_t* bytes) {
   if (!bytes || n < 1 || bias_len < 1 || n % bias_len)
     return fail(CG_ERR_ARG, "bias_act_workspace_bytes: bad arguments");

@@ -55,13 +55,18 @@ from .plan import plan_for
 from .trainer import FlatTrainer
 
 
-def _chain(scope, Fin, F, R, Fout_last):
-    """(name, Fin, Fout, act) of a residual network's filters in the reference's call order."""
-    layers = [(f"{scope}conv_init/weights", Fin, F, "relu")]
+ACTS = ("relu", "relu", "none")  # residual_network: after conv_init, in the layers, after convN
+
+
+def _chain(scope, Fin, F, R, Fout_last, acts=ACTS):
+    """(name, Fin, Fout, act) of a residual network's filters in the reference's call order.
+    ``acts``: the activation after conv_init, inside the residual layers, after the last filter."""
+    a_init, a_res, a_last = acts
+    layers = [(f"{scope}conv_init/weights", Fin, F, a_init)]
     for i in range(R):
-        layers.append((f"{scope}residual_layer_{i}/sublayer0/weights", F, F, "relu"))
-        layers.append((f"{scope}residual_layer_{i}/sublayer1/weights", F, F, "relu"))
-    layers.append((f"{scope}convN/weights", F, Fout_last, "none"))
+        layers.append((f"{scope}residual_layer_{i}/sublayer0/weights", F, F, a_res))
+        layers.append((f"{scope}residual_layer_{i}/sublayer1/weights", F, F, a_res))
+    layers.append((f"{scope}convN/weights", F, Fout_last, a_last))
     return layers
 
 
@@ -79,14 +84,15 @@ class _ResNet:
     ``input_grad``: the input is an activation, not data (the network sits
     behind an LSTM, lib/gconv_lstm.py:382-389): conv_init's backward also
     computes dx into ``dx_in`` [N, M, Fin].  ``names`` replaces the variable
-    names (same order)."""
+    names (same order).  ``acts``: the three activations of ``_chain`` (the
+    gconv networks of lib/gconv_lstm.py:297-372 use tanh, and end a branch in ReLU)."""
 
     def __init__(self, owner, scope: str, Fin: int, nfilter: int, K: int, R: int, Fout_last: int, gen,
-                 input_grad: bool = False, names=None):
+                 input_grad: bool = False, names=None, acts=ACTS):
         self.o = owner
         N, M = owner.N, owner.M
         self.Fin, self.K, self.R = Fin, K, R
-        self.layers = layers = _chain(scope, Fin, nfilter, R, Fout_last)
+        self.layers = layers = _chain(scope, Fin, nfilter, R, Fout_last, acts)
         self.names = list(names) if names is not None else [name for name, *_ in layers]
         if len(self.names) != len(layers):
             raise ValueError(f"{len(layers)} filters, {len(self.names)} names")
@@ -102,6 +108,8 @@ class _ResNet:
         # activations saved by the forward, gradient work buffers
         self.out = [torch.empty((N, M, fo), **f32) for _, _, fo, _ in layers]
         self.g = [torch.empty((N, M, nfilter), **f32) for _ in range(3)]
+        # a last filter with an activation: its dz, of the output's width
+        self.dz_last = torch.empty((N, M, Fout_last), **f32) if layers[-1][3] != "none" else None
         self._setup(f32)
 
     @staticmethod
@@ -163,7 +171,7 @@ class _ResNet:
         last = len(self.layers) - 1
         bufs = self.g
         dh = bufs[0]
-        self._b(last, dout, None, dh, False, s)            # convN: dh = dL/dh
+        self._b(last, dout, self.dz_last, dh, False, s)    # convN: dh = dL/dh
         cur = 0  # bufs[cur] is dh
         li = last - 2
         for _ in range(self.R):

@@ -123,7 +123,22 @@ def _supported(entry, *args) -> bool:
     return bool(ok.value)
 
 
-ACTS = {"none": _lib.CG_ACT_NONE, "relu": _lib.CG_ACT_RELU}
+ACTS = {"none": _lib.CG_ACT_NONE, "relu": _lib.CG_ACT_RELU, "tanh": _lib.CG_ACT_TANH}
+
+
+def act_forward_(y: torch.Tensor, residual: torch.Tensor | None = None, act: str = "none"):
+    """y <- act(y + residual) in place: the epilogue of the Chebyshev forward as
+    its own launch (what the routes without a fused store finish through)."""
+    _check_dev("y", y)
+    if not y.is_contiguous():
+        raise ValueError("y must be contiguous (it is written in place)")
+    if residual is not None:
+        _check_dev("residual", residual)
+        residual = residual.contiguous()
+        if residual.numel() != y.numel():
+            raise ValueError("residual must have y's size")
+    _lib.call("cg_act_forward", y.numel(), _p(y), _p(residual), ACTS[act], _stream(y))
+    return y
 
 
 def basis_layout_for(plan: ChebPlan, N: int, Fin: int, K: int, Fout: int) -> str:

@@ -186,13 +186,18 @@ int cg_cheb_backward(cg_plan* plan, int32_t N, int32_t Fin, int32_t K, int32_t F
  *   y = act(basis W + residual)       residual [N][M][Fout] or NULL, act CG_ACT_*
  * i.e. `x = self.filter(x, ...)`, `x = x + x_identity`, `x = b1relu(x)` in one
  * pass (the resident and streaming kernels apply it in their y store).
+ * CG_ACT_TANH is the residual layer of lib/gconv_lstm.py:642-658,
+ * tanh(filter(tanh(filter(x))) + x): the same approximation in every kernel (a
+ * few ulp), so all routes agree bitwise on the same pre-activation.
  * Backward through it: dz = dy * act'(y) with y the forward's OUTPUT (ReLU:
- * y > 0), written to dz (required when act != NONE; also the gradient of the
+ * y > 0; tanh: 1 - y^2), written to dz (required when act != NONE; also the gradient of the
  * residual input), then the filter backward on dz.  dx_accumulate != 0 adds
  * the filter's input gradient into dx (dx += ...) -- the gradient sum of a
  * tensor that feeds both a filter and a residual branch.
  * ------------------------------------------------------------------------- */
-enum { CG_ACT_NONE = 0, CG_ACT_RELU = 1, CG_ACT_TANH = 2 /* bias_act only */ };
+/* All three: the cg_cheb_*_ex / _layout entries, cg_act_forward, cg_bias_act_*.
+ * The Fourier entries cg_fres_* take NONE and RELU only. */
+enum { CG_ACT_NONE = 0, CG_ACT_RELU = 1, CG_ACT_TANH = 2 };
 int cg_cheb_forward_ex(cg_plan* plan, int32_t N, int32_t Fin, int32_t K, int32_t Fout,
                        const float* x, const float* W, const float* residual, int32_t act,
                        float* basis, float* y, void* workspace, size_t ws_bytes, void* stream);
@@ -200,6 +205,10 @@ int cg_cheb_backward_ex(cg_plan* plan, int32_t N, int32_t Fin, int32_t K, int32_
                         const float* dy, const float* y, int32_t act, const float* basis,
                         const float* W, float* dx, int32_t dx_accumulate, float* dW, float* dz,
                         void* workspace, size_t ws_bytes, void* stream);
+/* The same epilogue on its own, y[i] = act(y[i] + residual[i]) in place over n
+ * floats (residual NULL: no add; it may not alias y): what the routes whose
+ * contraction kernel has no epilogue finish through.  Additive to version 301. */
+int cg_act_forward(int64_t n, float* y, const float* residual, int32_t act, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Basis layouts.  The basis is the forward's saved tensor (the x of

@@ -20,6 +20,12 @@
       in both merge modes; and the two seams alone against their composition from
       existing ops
 
+  GC  the training step of the three pure graph-convolution networks (gconv_net.
+      GConvNetModel: inference_gconv, ..._period_no_expand, ..._period_expand) on config E's
+      graph at the driver's shape (batch 100, T=(3, 3, 3), num_hidden 64, K=2, 4 residual
+      layers, out 2) against the same network composed from ops.cheb_conv + add +
+      ops.bias_act under autograd, interleaved
+
   FIT the training loop around a step: ResGNN at config R's shape and GLSTMModel at config
       E's model step, 2 048 synthetic samples on the device -- (a) train_step on one static
       batch (the floor), (b) the loop a user writes without fit, train_step(data[i],
@@ -32,7 +38,7 @@ rounds; alg_GBps uses SURVEY.md §8d's algorithmic bytes.  Each line carries a
 `cpu_baseline`: the oracle's fwd+bwd of the same config on the host cores
 (bench.py's CPU legs -- the only place outside tests/ that runs oracle/),
 median of the timed passes, with the sub-batch and pass count stated.
-Usage: python scripts/bench_configs.py [A C1 C2 D E EF EP FIT R RF S] [--d-batch N] [--layout auto|rows|planes]
+Usage: python scripts/bench_configs.py [A C1 C2 D E EF EP FIT GC R RF S] [--d-batch N] [--layout auto|rows|planes]
                                        [--no-cpu] [--cpu-seconds S]
 """
 from __future__ import annotations
@@ -486,6 +492,77 @@ def period_config(dev, N=50, T=(3, 3, 3), Fin=2, K=2, keep=0.8, runs=5):
     return out
 
 
+def gconv_net_config(dev, N=100, T=(3, 3, 3), H=64, K=2, nres=4, out_f=2, runs=5):
+    """GC: one GConvNetModel training step of each of the three pure graph-
+    convolution networks at the driver's shape (nips2016/gconvTest.py: grid(32)
+    8-NN, M = 1024, batch 100, T = (3, 3, 3) so C = 18, num_hidden 64, kernel_num
+    2, conv_layer_num 4, out 2), against the same network composed from the
+    unfused ops under autograd: ops.cheb_conv, a torch add for the residual,
+    ops.bias_act for the activation, ops.mse_loss and one ops.adam_update per
+    variable, on copies of the model's weights.  HIP events, fused and unfused
+    interleaved run by run; per-run numbers, medians and the unfused range."""
+    from cnn_graph_amd import gconv_net as GN
+    _, L = graph_e()
+    M = L.shape[0]
+    g = torch.Generator(device=dev)
+    g.manual_seed(10)
+    C = GN.FLOWS * sum(T)
+    x = 0.5 * torch.randn((N, M, C), device=dev, generator=g)
+    labels = torch.randn((N, M, out_f), device=dev, generator=g)
+    legs = {}
+    for fn in GN.INFER_FUNCS:
+        model = GN.GConvNetModel(L, N, T=T, num_hidden=H, K=K, conv_layer_num=nres, out_features=out_f,
+                                 infer_func=fn, device=dev)
+        Ws = [w.detach().clone().requires_grad_() for w in model.W]
+        slots = [(torch.zeros_like(w), torch.zeros_like(w)) for w in Ws]
+        plan, per = model.plan, 2 * nres + 2
+        count = [0]
+
+        def act(v, a):
+            return v if a == "none" else ops.bias_act(v, None, a)
+
+        def net(h, ws, acts):
+            a_init, a_res, a_last = acts
+            h = act(ops.cheb_conv(h, ws[0], plan, K), a_init)
+            for i in range(nres):
+                t = act(ops.cheb_conv(h, ws[1 + 2 * i], plan, K), a_res)
+                h = act(ops.cheb_conv(t, ws[2 + 2 * i], plan, K) + h, a_res)
+            return act(ops.cheb_conv(h, ws[per - 1], plan, K), a_last)
+
+        def unfused(fn=fn, Ws=Ws, slots=slots, net=net, count=count, model=model):
+            if fn in GN.SINGLE:
+                out = net(x, Ws, GN.SINGLE[fn])
+            else:
+                outs = [net(x[:, :, a:b].contiguous(), Ws[j * per:(j + 1) * per], GN.EXPAND_ACTS)
+                        for j, (a, b) in enumerate(model.columns)]
+                out = ops.cheb_conv(torch.cat(outs, dim=2), Ws[-1], plan, K)
+            _, dout = ops.mse_loss(out, labels)
+            out.backward(dout)
+            count[0] += 1
+            for w, (m, v) in zip(Ws, slots):
+                ops.adam_update(w.data, w.grad, m, v, count[0])
+                w.grad = None
+
+        legs[fn] = (lambda model=model: model.train_step(x, labels), unfused)
+    for fused, unf in legs.values():  # warm every shape of the timed window
+        for _ in range(3):
+            fused(), unf()
+    torch.cuda.synchronize()
+    res = {}
+    for fn, (fused, unf) in legs.items():
+        r = {"fused": [], "unfused": []}
+        for _ in range(runs):
+            r["fused"].append(round(ev_ms(fused, 5), 4))
+            r["unfused"].append(round(ev_ms(unf, 5), 4))
+        med = {k: round(float(np.median(v)), 4) for k, v in r.items()}
+        res[fn] = {"runs_ms": r, "median_ms": med, "unfused_range_ms": [min(r["unfused"]), max(r["unfused"])],
+                   "fused_range_ms": [min(r["fused"]), max(r["fused"])],
+                   "fused_below_unfused_range": bool(med["fused"] < min(r["unfused"])),
+                   "samples_per_s": round(N / (med["fused"] * 1e-3), 1)}
+    return {"config": "GC", "M": M, "N": N, "T": list(T), "C": C, "H": H, "K": K, "conv_layer_num": nres,
+            "out": out_f, "steps": res}
+
+
 def seq_head_config(dev, T=12, N=128, Fin=2, H=32, K=3, keep=0.8, runs=5):
     """S: the gconvRNN sequence model (gconv_rnn.GConvRNNModel) at config E's
     graph and shape.  (a) the fused head (cg_seq_xent_head: mask, logits,
@@ -710,6 +787,8 @@ def main():
             out = period_config(dev)
         elif name == "FIT":
             out = fit_config(dev)
+        elif name == "GC":
+            out = gconv_net_config(dev)
         elif name == "R":
             out = resgnn_config(dev)
             cpu = lambda: bench.cpu_baseline_resgnn(graph_e()[1], 2, 100, 2, 32, 20, 4,  # noqa: E731
