@@ -85,7 +85,7 @@ from . import _lib
 from . import ops
 from .graph_conv import truncated_normal_
 from .plan import plan_for
-from .trainer import FlatTrainer
+from .trainer import DropoutEval, FlatTrainer, check_keep_prob, is_fourier_conv
 
 # distinct default mask streams per DropoutWrapper (TF: one random op each)
 _DROPOUT_ORDINAL = itertools.count(1)
@@ -633,10 +633,8 @@ class DropoutWrapper:
     ordinal), so two same-shaped layers never share masks."""
 
     def __init__(self, cell: GConvLSTMCell, output_keep_prob: float = 1.0, seed: int | None = None):
-        if not 0.0 < float(output_keep_prob) <= 1.0:
-            raise ValueError(f"output_keep_prob must be in (0, 1], got {output_keep_prob}")
         self.cell = cell
-        self.output_keep_prob = float(output_keep_prob)
+        self.output_keep_prob = check_keep_prob(output_keep_prob, "output_keep_prob")
         if seed is None:
             seed = (torch.initial_seed() * 0x9E3779B97F4A7C15 + next(_DROPOUT_ORDINAL) * 0xBF58476D1CE4E5B9)
         self._seed = int(seed) & ((1 << 64) - 1)
@@ -792,19 +790,19 @@ def wrap_cells(cells, keep_prob, seed, comm, first: int = 0):
             if keep_prob < 1.0 else c for li, c in enumerate(cells)]
 
 
-class LSTMStackTrainer(FlatTrainer):
-    """The part ``GLSTMModel`` and ``GLSTMGconvModel`` share: ``glstm_layer``
-    (lib/gconv_lstm.py:609-627) -- layer_count GConvLSTMCells, each in a
-    DropoutWrapper(keep_prob) -- with every cell's Wx, Wh, b carved from the flat
-    buffers first, as autograd-owned Parameters whose ``.grad`` is the bucket
+class LSTMStackTrainer(DropoutEval, FlatTrainer):
+    """The part ``GLSTMModel``, ``GLSTMGconvModel`` and ``GConvRNNModel`` share:
+    ``glstm_layer`` (lib/gconv_lstm.py:609-627) -- layer_count GConvLSTMCells, each
+    in a DropoutWrapper(keep_prob) -- with every cell's Wx, Wh, b carved from the
+    flat buffers first, as autograd-owned Parameters whose ``.grad`` is the bucket
     view.  ``tail_numel`` parameters follow, for the subclass to carve (drawing
-    from ``self._gen``, after the cells' own initial draws)."""
+    from ``self._gen``, after the cells' own initial draws).  ``head``: a residual
+    head follows (``_graph_from_cell``'s ``gft``)."""
 
     def __init__(self, L, N, T, feat_in, num_hidden, K, layer_count, out_features, keep_prob, filter,
                  tail_numel, optimizer, learning_rate, decay_rate, decay_steps, lmax, gates, device,
-                 seed, comm, hconv="auto"):
-        if filter not in ("cheby_conv", "fourier_conv"):
-            raise ValueError("filter must be 'cheby_conv' or 'fourier_conv'")
+                 seed, comm, hconv="auto", head=False):
+        is_fourier_conv(filter)
         self.filter = filter
         self.N, self.T, self.F, self.H, self.K = int(N), int(T), int(feat_in), int(num_hidden), int(K)
         self.Fout = int(out_features)
@@ -812,13 +810,10 @@ class LSTMStackTrainer(FlatTrainer):
         self._gen = gen = torch.Generator(device=device)
         gen.manual_seed(seed)
         cells = make_cells(L, self.F, self.H, self.K, layer_count, lmax, gates, device, gen, filter, hconv)
-        self.M = cells[0]._nNode
         super().__init__(sum(p.numel() for c in cells for p in c.parameters()) + tail_numel,
-                         (self.N, self.M, self.Fout), optimizer, learning_rate, decay_rate, decay_steps,
-                         device, comm)
-        fourier = filter == "fourier_conv"
-        self.plan = None if fourier else cells[0].plan
-        self.U = cells[0].U if fourier else None
+                         (self.N, cells[0]._nNode, self.Fout), optimizer, learning_rate, decay_rate,
+                         decay_steps, device, comm)
+        self._graph_from_cell(cells[0], gft=head)
         carve_cells(self, cells)
         self.cells = cells
         self.wrapped = wrap_cells(cells, keep_prob, seed, comm)
@@ -827,26 +822,6 @@ class LSTMStackTrainer(FlatTrainer):
         if x.dim() == 3:  # [N, M, F*T] as the reference feeds it
             return unstack_time(x, self.T)
         return x.contiguous()
-
-    def predict(self, data, labels=None, reference_dropout: bool = False):
-        """GraphModel.predict (lib/graph_model.py:64-94; evaluate.predict has the
-        padding and the ``loss * batch_size / size`` quirk, padded rows
-        included): data [size, M, F*T] -> predictions [size, M, out_features],
-        with labels also the loss.  Parameters, optimizer slots, the loss
-        average and the step count are untouched.
-
-        Dropout at evaluation: the reference's DropoutWrapper(0.8) inside
-        glstm_layer (lib/gconv_lstm.py:616, :623) is a constant of the graph, so
-        the reference ALSO drops when it evaluates.  The default here is no
-        dropout (deterministic predictions); ``reference_dropout=True`` applies
-        the wrappers' masks as a training forward does (and advances their
-        mask streams)."""
-        return super().predict(data, labels, dropout=reference_dropout)
-
-    def evaluate(self, data, labels, reference_dropout: bool = False):
-        """GraphModel.evaluate (lib/graph_model.py:96-122):
-        (string, mse, 0, loss, predictions)."""
-        return super().evaluate(data, labels, dropout=reference_dropout)
 
 
 class GLSTMModel(LSTMStackTrainer):
@@ -886,25 +861,25 @@ class GLSTMModel(LSTMStackTrainer):
                                self._gen)
         self.W_fc = self.carve(fc_shape, "conv_init/weights", init=w0)[0]
         self._carved()
+        self._out = None
 
-    def forward(self, x, dropout: bool = True):
+    def forward(self, x, dropout: bool = True, stream=None):
         """inference_glstm: the fc layer's output [N, M, out_features] (lstm_to_hT,
         the last-step mask through ops.dropout, fc_layer).  ``dropout=False``
-        runs every layer unwrapped."""
+        runs every layer unwrapped.  Every launch goes to torch's current stream;
+        ``stream`` is train_step's and must be that stream.  ``backward`` continues
+        from the output this call keeps."""
         h, mask = lstm_to_hT(self.cells, self.wrapped, self._steps(x), dropout)
         if mask is not None:
             keep, seed, off = mask
             h = ops.dropout(h, keep, seed, offset=off)
-        if self.filter == "fourier_conv":
-            return ops.fourier_conv(h, self.W_fc, self.U)
-        return ops.cheb_conv(h, self.W_fc, self.plan, self.K)
+        self._out = ops.fourier_conv(h, self.W_fc, self.U) if self.filter == "fourier_conv" \
+            else ops.cheb_conv(h, self.W_fc, self.plan, self.K)
+        return self._out
 
-    def train_step(self, x, labels, stream=None):
-        """One optimizer step; returns the device loss [1] (this rank's batch)."""
-        s = self._stream(stream)
+    def backward(self, dout, stream=None):
+        """Every gradient of the last forward from d(out): autograd, accumulating
+        into the (zeroed) bucket."""
         self.grad.zero_()
-        out = self.forward(x)
-        self._loss(out, labels, s)
-        out.backward(self.dout)
-        self._exchange_and_update(s)
-        return self.loss
+        out, self._out = self._out, None
+        out.backward(dout)

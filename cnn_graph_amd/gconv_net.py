@@ -40,12 +40,9 @@ import ctypes
 import torch
 
 from . import _lib
-from . import filter as _filter
-from . import ops
 from .graph_conv import truncated_normal_
-from .model import _FourierResNet, _ResNet
-from .plan import plan_for
-from .trainer import FlatTrainer
+from .model import _ChannelSplit, _ChebFilter, _net_class, head_names
+from .trainer import FlatTrainer, is_fourier_conv
 
 # infer_func -> (after conv_init, inside the residual layers, after the last filter)
 SINGLE = {"inference_gconv": ("tanh", "tanh", "none"),
@@ -67,16 +64,9 @@ def variable_names(infer_func: str, conv_layer_num: int):
     """The reference's variable names in creation order."""
     if infer_func not in INFER_FUNCS:
         raise ValueError(f"infer_func must be one of {INFER_FUNCS}, got {infer_func!r}")
-
-    def net(j):
-        names = [f"conv_init{j}/weights"]
-        for i in range(conv_layer_num):
-            names += [f"conv_layer_{i}{j}/residual_layer_{i}/sublayer{k}/weights" for k in (0, 1)]
-        return names + [f"output_layer{j}/weights"]
-
     if infer_func in SINGLE:
-        return net("")
-    return [n for j in range(3) for n in net(f"_{j}")] + ["merge_layer/weights"]
+        return head_names(conv_layer_num)
+    return [n for j in range(3) for n in head_names(conv_layer_num, f"_{j}")] + ["merge_layer/weights"]
 
 
 def _check_T(T):
@@ -104,9 +94,7 @@ class GConvNetModel(FlatTrainer):
                  in_features: int | None = None):
         if infer_func not in INFER_FUNCS:
             raise ValueError(f"infer_func must be one of {INFER_FUNCS}, got {infer_func!r}")
-        if filter not in ("cheby_conv", "fourier_conv"):
-            raise ValueError("filter must be 'cheby_conv' or 'fourier_conv'")
-        fourier = filter == "fourier_conv"
+        fourier = is_fourier_conv(filter)
         if fourier and (infer_func == EXPAND or "tanh" in SINGLE[infer_func]):
             raise NotImplementedError(
                 f"{infer_func} with filter='fourier_conv': the Fourier store has no tanh (cg_fres_* take "
@@ -123,7 +111,7 @@ class GConvNetModel(FlatTrainer):
             self.C = int(in_features)
         self.columns = branch_columns(self.T)
         M, H, K, R, Fout = int(L.shape[0]), self.H, self.K, self.R, self.Fout
-        net = _FourierResNet if fourier else _ResNet
+        net = _net_class(fourier)
         expand = infer_func == EXPAND
         if expand:
             total = sum(sum(net.sizes(b - a, H, K, M, R, Fout)) for a, b in self.columns)
@@ -132,13 +120,7 @@ class GConvNetModel(FlatTrainer):
             total = sum(net.sizes(self.C, H, K, M, R, Fout))
         super().__init__(total, (self.N, M, Fout), optimizer, learning_rate, decay_rate, decay_steps,
                          device, comm)
-        if fourier:  # no Chebyshev plan: U, prepared once for the transforms
-            self.plan, self.M = None, M
-            self.U = _filter.fourier_basis(L, self.device)
-            self.gft = ops.gft_prepare(self.U)
-        else:
-            self.plan = plan_for(L, lmax=lmax, device=self.device.index if self.device.index is not None else 0)
-            self.M = self.plan.M
+        self._set_graph(L, fourier, lmax)
         gen = torch.Generator(device=self.device)
         gen.manual_seed(seed)
         names = variable_names(infer_func, R)
@@ -153,13 +135,15 @@ class GConvNetModel(FlatTrainer):
             self.merge_W, self.merge_dW = self.carve((3 * Fout * K, Fout), names[-1])
             truncated_normal_(self.merge_W, 0.1, gen)
             Nb, Fc = self.N, 3 * Fout
-            self.x_b = [torch.empty((Nb, self.M, b - a), **f32) if (a, b) != (0, self.C) else None
-                        for a, b in self.columns]
+            self.split = _ChannelSplit(self, self.C, self.columns)
+            self.x_b = self.split.bufs
             self.cat = torch.empty((Nb, self.M, Fc), **f32)
             self.dcat = torch.empty((Nb, self.M, Fc), **f32)
             self.d_b = [torch.empty((Nb, self.M, Fout), **f32) for _ in range(3)]
             self.out = torch.empty((Nb, self.M, Fout), **f32)
-            self.merge_basis = torch.empty((Nb * self.M, Fc * K), **f32)
+            # merge_layer: ONE filter [3 out -> out] with dx, its basis in the rows layout
+            self.merge = _ChebFilter(self, Fc, Fout, K, "none", self.merge_W, self.merge_dW, self.out,
+                                     layout="rows")
             # the seams' host arrays of sizes / pointers / (unused) seeds, built once
             self._cat_H = (ctypes.c_int32 * 3)(Fout, Fout, Fout)
             self._cat_seed = (ctypes.c_uint64 * 3)(0, 0, 0)
@@ -167,16 +151,9 @@ class GConvNetModel(FlatTrainer):
             self._cat_d = (ctypes.c_void_p * 3)(*[d.data_ptr() for d in self.d_b])
         self._carved()
         self.W, self.dW = self._tensors, self._grads
-        self._alloc_ws(self.nets)
-        if expand:
-            merge_ws = max(self.plan.workspace_bytes(self.N, 3 * Fout, K, Fout))
-            if merge_ws > self.ws_n:
-                self.ws_n = merge_ws
-                self.ws = torch.empty(merge_ws, device=self.device, dtype=torch.uint8)
+        self._alloc_ws(self.nets + ([self.merge] if expand else []))
         h = _lib.lib()
-        self._slice, self._cat_f, self._cat_b = (h.cg_slice_channels, h.cg_concat_drop_forward,
-                                                 h.cg_concat_drop_backward)
-        self._fwd, self._bwd = h.cg_cheb_forward_layout, h.cg_cheb_backward_layout
+        self._cat_f, self._cat_b = h.cg_concat_drop_forward, h.cg_concat_drop_backward
 
     def forward(self, x, stream=None):
         """The network's output [N, M, out_features]."""
@@ -186,47 +163,22 @@ class GConvNetModel(FlatTrainer):
         x = x.contiguous()
         if self.infer_func != EXPAND:
             return self.nets[0].forward(x, s)
-        N, M, K, Fout = self.N, self.M, self.K, self.Fout
-        for (a, b), xb, net in zip(self.columns, self.x_b, self.nets):
-            xi = x
-            if xb is not None:
-                xi = xb
-                _lib.check("cg_slice_channels", self._slice(x.data_ptr(), N * M, self.C, a, b, xi.data_ptr(), s))
+        for net, xi in zip(self.nets, self.split.slices(x, s)):
             net.forward(xi, s)
         _lib.check("cg_concat_drop_forward",
-                   self._cat_f(3, N, M, self._cat_H, self._cat_in, ctypes.c_float(1.0), self._cat_seed,
-                               self.cat.data_ptr(), s))
-        _lib.check("cg_cheb_forward_layout",
-                   self._fwd(self.plan.handle, N, 3 * Fout, K, Fout, self.cat.data_ptr(),
-                             self.merge_W.data_ptr(), None, _lib.CG_ACT_NONE, _lib.CG_BASIS_ROWS,
-                             self.merge_basis.data_ptr(), self.out.data_ptr(), self.ws.data_ptr(),
-                             self.ws_n, s))
-        return self.out
+                   self._cat_f(3, self.N, self.M, self._cat_H, self._cat_in, ctypes.c_float(1.0),
+                               self._cat_seed, self.cat.data_ptr(), s))
+        return self.merge.forward(self.cat, None, s)
 
     def backward(self, dout, stream=None):
         """Every dW of the last forward from d(out) [N, M, out_features]."""
         s = self._stream(stream)
         dout = dout.contiguous()
         if self.infer_func != EXPAND:
-            self.nets[0].backward(dout, s)
-            return
-        N, M, K, Fout = self.N, self.M, self.K, self.Fout
-        _lib.check("cg_cheb_backward_layout",
-                   self._bwd(self.plan.handle, N, 3 * Fout, K, Fout, dout.data_ptr(), None,
-                             _lib.CG_ACT_NONE, _lib.CG_BASIS_ROWS, self.merge_basis.data_ptr(),
-                             self.merge_W.data_ptr(), self.dcat.data_ptr(), 0, self.merge_dW.data_ptr(),
-                             None, self.ws.data_ptr(), self.ws_n, s))
+            return self.nets[0].backward(dout, s)
+        self.merge.backward(dout, None, self.dcat, False, s)
         _lib.check("cg_concat_drop_backward",
-                   self._cat_b(3, N, M, self._cat_H, self.dcat.data_ptr(), ctypes.c_float(1.0),
+                   self._cat_b(3, self.N, self.M, self._cat_H, self.dcat.data_ptr(), ctypes.c_float(1.0),
                                self._cat_seed, self._cat_d, s))
         for net, d in zip(self.nets, self.d_b):
             net.backward(d, s)
-
-    def train_step(self, x, labels, stream=None):
-        """One optimizer step (lib/graph_model.py:277-310); returns the device loss [1]."""
-        s = self._stream(stream)
-        out = self.forward(x, s)
-        self._loss(out, labels, s)
-        self.backward(self.dout, s)
-        self._exchange_and_update(s)
-        return self.loss

@@ -44,7 +44,7 @@ import torch
 
 from . import ops
 from .gconv_lstm import LSTMStackTrainer, layer
-from .trainer import FlatTrainer
+from .trainer import FlatTrainer, check_keep_prob, check_seam
 
 # what seam="auto" resolves to ("The per-step softmax head": the rule
 # and the measurement)
@@ -62,18 +62,14 @@ class GConvRNNModel(LSTMStackTrainer):
                  learning_rate: float = 1e-3, max_grad_norm: float | None = None, lmax: float = 2,
                  filter: str = "cheby_conv", layer_count: int = 1, hconv: str = "auto", device=None,
                  seed: int = 2017, comm=None):
-        if seam not in ("auto", "fused", "unfused"):
-            raise ValueError("seam must be 'auto', 'fused' or 'unfused'")
-        if not 0.0 < float(keep_prob) <= 1.0:
-            raise ValueError(f"keep_prob must be in (0, 1], got {keep_prob}")
+        self.seam = AUTO_SEAM if check_seam(seam) == "auto" else seam
+        self.keep_prob = check_keep_prob(keep_prob)
         if max_grad_norm is not None and not float(max_grad_norm) > 0:
             raise ValueError("max_grad_norm must be positive (or None)")
         H = int(num_hidden)
         # constant learning rate: decay_rate = 1 (the reference's optimizers take a float)
         super().__init__(L, N, T, feat_in, H, K, layer_count, 1, keep_prob, filter, H + 1, optimizer,
                          learning_rate, 1, None, lmax, "standard", device, seed, comm, hconv=hconv)
-        self.seam = AUTO_SEAM if seam == "auto" else seam
-        self.keep_prob = float(keep_prob)
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         f32 = dict(device=self.device, dtype=torch.float32)
         w0 = torch.empty((H, 1), **f32).normal_(0.0, 1.0, generator=self._gen)
@@ -143,7 +139,8 @@ class GConvRNNModel(LSTMStackTrainer):
 
     def train_step(self, x, labels, stream=None, with_output: bool = False):
         """``train`` (:361-369): one optimizer step; returns the device loss [1]
-        of this rank's batch (and pred_out with ``with_output``)."""
+        of this rank's batch (and pred_out with ``with_output``).  Its own step, not
+        FlatTrainer's: the loss is the per-step softmax head's, not ``_loss``."""
         s = self._stream(stream)
         lab = self._labels(labels)
         self.grad.zero_()

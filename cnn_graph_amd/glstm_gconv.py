@@ -33,17 +33,16 @@ driver's shape ("The LSTM -> head seam").
 """
 from __future__ import annotations
 
-import torch
-
 from . import ops
 from .gconv_lstm import LSTMStackTrainer, lstm_to_hT
-from .model import _FourierResNet, _ResNet
+from .model import LSTMHead, _net_class
+from .trainer import check_keep_prob, check_seam
 
 # what "auto" resolves to for the Fourier head (DESIGN.md has the measurement)
 AUTO_SEAM = "fused"
 
 
-class GLSTMGconvModel(LSTMStackTrainer):
+class GLSTMGconvModel(LSTMHead, LSTMStackTrainer):
     """inference_glstm_gconv on device.  Every parameter -- each layer's Wx, Wh,
     b, then conv_init, the residual layers and output_layer -- is a view into one
     flat fp32 buffer, every gradient a view into one flat bucket."""
@@ -54,36 +53,20 @@ class GLSTMGconvModel(LSTMStackTrainer):
                  seam: str = "auto", optimizer: str = "adam", learning_rate: float = 1e-3,
                  decay_rate: float = 0.95, decay_steps: int | None = None, lmax: float = 2,
                  gates: str = "reference", device=None, seed: int = 2017, comm=None):
-        if seam not in ("auto", "fused", "unfused"):
-            raise ValueError("seam must be 'auto', 'fused' or 'unfused'")
-        if not 0.0 < float(keep_prob) <= 1.0:
-            raise ValueError(f"keep_prob must be in (0, 1], got {keep_prob}")
+        check_seam(seam)
+        self.keep_prob = check_keep_prob(keep_prob)
         fourier = filter == "fourier_conv"
         if seam == "fused" and not fourier:
             raise ValueError("seam='fused' folds the mask into the Fourier transforms; the "
                              "Chebyshev head is 'unfused'")
         self.seam = (AUTO_SEAM if fourier else "unfused") if seam == "auto" else seam
-        self.keep_prob = float(keep_prob)
         H, C, R, Fout = int(num_hidden), int(num_hidden_conv), int(conv_layer_num), int(out_features)
         self.R = R
-        net = _FourierResNet if fourier else _ResNet
         super().__init__(L, N, T, feat_in, num_hidden, K, layer_count, out_features, keep_prob, filter,
-                         sum(net.sizes(H, C, int(K), int(L.shape[0]), R, Fout)), optimizer,
-                         learning_rate, decay_rate, decay_steps, lmax, gates, device, seed, comm)
-        self.lstm_grad = self.grad[:self._off]  # what autograd accumulates into
-        head_names = ["conv_init/weights"]
-        for i in range(R):
-            head_names += [f"conv_layer_{i}/residual_layer_{i}/sublayer{j}/weights" for j in (0, 1)]
-        head_names.append("output_layer/weights")
-        if fourier:
-            c0 = self.cells[0]
-            self.gft = c0.gft_basis if c0.gft_basis is not None else ops.gft_prepare(self.U)
-        # truncated_normal(0, 0.1) on the flat views (lib/filter.py:39, :63), after the cells' draws
-        self.head = net(self, "", H, C, self.K, R, Fout, self._gen, input_grad=True, names=head_names)
+                         sum(_net_class(fourier).sizes(H, C, int(K), int(L.shape[0]), R, Fout)), optimizer,
+                         learning_rate, decay_rate, decay_steps, lmax, gates, device, seed, comm, head=True)
+        self._make_head(fourier, H, C, R, Fout, self._gen)
         self._carved()
-        self.head_W, self.head_dW = self.head.W, self.head.dW
-        self._alloc_ws([self.head])
-        self._h = None
 
     def forward(self, x, stream=None, dropout: bool = True):
         """The output layer's [N, M, out_features] (a buffer the next forward
@@ -95,15 +78,15 @@ class GLSTMGconvModel(LSTMStackTrainer):
         if tuple(xs.shape) != (self.T, self.N, self.M, self.F) or not xs.is_cuda:
             raise ValueError(f"x must be a cuda tensor of [N, M, F*T] = {(self.N, self.M, self.F * self.T)}")
         h, mask = lstm_to_hT(self.cells, self.wrapped, xs, dropout)
-        self.head.drop = None
+        drop = None
         if mask is not None:
             keep, seed, off = mask
-            if self.seam == "fused":
-                self.head.drop = (keep, (seed + ops.DROP_WEYL * off) & ((1 << 64) - 1))
+            if self.seam == "fused":  # conv_init reads h_T through the mask
+                drop = (keep, (seed + ops.DROP_WEYL * off) & ((1 << 64) - 1))
             else:
                 h = ops.dropout(h, keep, seed, offset=off)
-        self._h = h  # what conv_init read (through the mask when fused)
-        return self.head.forward(h.detach().contiguous(), s)
+        self.head.filters[0].drop = drop
+        return self._head_forward(h, s)
 
     def backward(self, dout, stream=None):
         """Every gradient of the last forward from d(out) [N, M, out_features]: the
@@ -111,18 +94,4 @@ class GLSTMGconvModel(LSTMStackTrainer):
         dx -- already through the mask when the seam is fused -- as dh_T of the
         LSTM, whose layers accumulate into the (zeroed) bucket through autograd;
         an input that requires grad gets its ``.grad``."""
-        s = self._stream(stream)
-        self.lstm_grad.zero_()
-        self.head.backward(dout.contiguous(), s)
-        if self._h is not None and self._h.requires_grad:
-            self._h.backward(self.head.dx_in)
-        self._h = None
-
-    def train_step(self, x, labels, stream=None):
-        """One optimizer step; returns the device loss [1] (this rank's batch)."""
-        s = self._stream(stream)
-        out = self.forward(x, stream)
-        self._loss(out, labels, s)
-        self.backward(self.dout, stream)
-        self._exchange_and_update(s)
-        return self.loss
+        self._head_backward(dout, self._stream(stream))

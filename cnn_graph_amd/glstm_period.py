@@ -45,8 +45,8 @@ import torch
 from . import ops
 from .gconv_lstm import carve_cells, lstm_to_hT, make_cells, unstack_time, wrap_cells
 from .graph_conv import truncated_normal_
-from .model import _FourierResNet, _ResNet
-from .trainer import FlatTrainer
+from .model import LSTMHead, _net_class
+from .trainer import DropoutEval, FlatTrainer, check_keep_prob, is_fourier_conv
 
 # infer_func -> the scope of the branch filter's variable below merge_{b}/
 # (fc_layer opens conv_init, :631-633; gconv1 calls the filter in merge_{b} itself)
@@ -63,7 +63,7 @@ REFUSED = {
 INFER_FUNCS = tuple(WEIGHT_MERGE) + tuple(CONCAT_MERGE)
 
 
-class GLSTMPeriodModel(FlatTrainer):
+class GLSTMPeriodModel(LSTMHead, DropoutEval, FlatTrainer):
     """The multi-branch gconv-LSTM on device; ``infer_func`` selects the network
     by the reference's name (``INFER_FUNCS``).  T = (Tc, Tp, Tt): the steps of
     the closeness, period and trend windows."""
@@ -78,10 +78,8 @@ class GLSTMPeriodModel(FlatTrainer):
             raise NotImplementedError(REFUSED[infer_func])
         if infer_func not in INFER_FUNCS:
             raise ValueError(f"infer_func must be one of {INFER_FUNCS}, got {infer_func!r}")
-        if filter not in ("cheby_conv", "fourier_conv"):
-            raise ValueError("filter must be 'cheby_conv' or 'fourier_conv'")
-        if not 0.0 < float(keep_prob) <= 1.0:
-            raise ValueError(f"keep_prob must be in (0, 1], got {keep_prob}")
+        fourier = is_fourier_conv(filter)
+        self.keep_prob = check_keep_prob(keep_prob)
         self.infer_func, self.filter = infer_func, filter
         self.concat = infer_func in CONCAT_MERGE
         T = tuple(int(t) for t in ((T,) if isinstance(T, int) else T))
@@ -91,14 +89,13 @@ class GLSTMPeriodModel(FlatTrainer):
             raise ValueError(f"T must hold 1 to {ops.MAX_BRANCHES} positive step counts, got {T}")
         self.T, self.B = T, len(T)
         self.N, self.F, self.H, self.K = int(N), int(feat_in), int(num_hidden), int(K)
-        self.Fout, self.R, self.keep_prob = int(out_features), int(conv_layer_num), float(keep_prob)
+        self.Fout, self.R = int(out_features), int(conv_layer_num)
         # branch b's first column / F (the prefix sums of T)
         self.S = [sum(T[:b]) for b in range(self.B)]
         self.C = self.F * sum(T)  # the columns the branches read
         device = torch.device(device if device is not None else "cuda")
-        fourier = filter == "fourier_conv"
         M, H, Fout, B = int(L.shape[0]), self.H, self.Fout, self.B
-        self._gen = gen = torch.Generator(device=device)
+        gen = torch.Generator(device=device)
         gen.manual_seed(seed)
         f32 = dict(device=device, dtype=torch.float32)
         fc_shape = (M, Fout, H) if fourier else (self.K * H, Fout)
@@ -110,8 +107,6 @@ class GLSTMPeriodModel(FlatTrainer):
             if not self.concat:
                 tails.append((truncated_normal_(torch.empty(fc_shape, **f32), 0.1, gen),
                               truncated_normal_(torch.empty((M, Fout), **f32), 0.1, gen)))
-        self.M = branches[0][0]._nNode
-        net = _FourierResNet if fourier else _ResNet
         total = 0
         for b, cells in enumerate(branches):
             # every branch's cells start 16-byte aligned (FlatTrainer.align): the layer
@@ -120,12 +115,10 @@ class GLSTMPeriodModel(FlatTrainer):
             total += -total % 4 + sum(p.numel() for c in cells for p in c.parameters())
             total += sum(t.numel() for t in tails[b]) if tails else 0
         if self.concat:
-            total += sum(net.sizes(B * H, H, self.K, M, self.R, Fout))
-        super().__init__(total, (self.N, self.M, Fout), optimizer, learning_rate, decay_rate,
-                         decay_steps, device, comm)
-        c0 = branches[0][0]
-        self.plan = None if fourier else c0.plan
-        self.U = c0.U if fourier else None
+            total += sum(_net_class(fourier).sizes(B * H, H, self.K, M, self.R, Fout))
+        super().__init__(total, (self.N, branches[0][0]._nNode, Fout), optimizer, learning_rate,
+                         decay_rate, decay_steps, device, comm)
+        self._graph_from_cell(branches[0][0], gft=self.concat)
         self.cells, self.wrapped = branches, []
         self.fc_W, self.merge_w = [], []
         for b, cells in enumerate(branches):
@@ -138,22 +131,10 @@ class GLSTMPeriodModel(FlatTrainer):
                 W, w = tails[b]
                 self.fc_W.append(self.carve(fc_shape, f"{scope}{WEIGHT_MERGE[infer_func]}weights", init=W)[0])
                 self.merge_w.append(self.carve((M, Fout), f"{scope}weight_{b}/weights", init=w)[0])
-        self.head = None
-        if self.concat:
-            self.lstm_grad = self.grad[:self._off]  # what autograd accumulates into
-            names = ["conv_init/weights"]
-            for i in range(self.R):
-                names += [f"conv_layer_{i}/residual_layer_{i}/sublayer{j}/weights" for j in (0, 1)]
-            names.append("output_layer/weights")
-            if fourier:
-                self.gft = c0.gft_basis if c0.gft_basis is not None else ops.gft_prepare(self.U)
-            # truncated_normal(0, 0.1) on the flat views (lib/filter.py:39, :63), after the
-            # branches' draws; its width is num_hidden (:455, :594)
-            self.head = net(self, "", B * H, H, self.K, self.R, Fout, gen, input_grad=True, names=names)
-            self.head_W, self.head_dW = self.head.W, self.head.dW
-            self._alloc_ws([self.head])
+        if self.concat:  # the head's width is num_hidden (:455, :594)
+            self._make_head(fourier, B * H, H, self.R, Fout, gen)
         self._carved()
-        self._out = self._a = None
+        self._out = None
 
     # -- the input split (:472-479, :486-487) ------------------------------------------------
     def split(self, x):
@@ -184,8 +165,7 @@ class GLSTMPeriodModel(FlatTrainer):
             if masks[0] is not None:
                 keep = masks[0][0]
                 seeds = [(seed + ops.DROP_WEYL * off) & ((1 << 64) - 1) for _, seed, off in masks]
-            self._a = ops.concat_drop(hs, keep, seeds)  # what conv_init reads
-            return self.head.forward(self._a.detach(), s)
+            return self._head_forward(ops.concat_drop(hs, keep, seeds), s)
         ys = []
         for h, mask, W in zip(hs, masks, self.fc_W):
             if mask is not None:
@@ -196,42 +176,16 @@ class GLSTMPeriodModel(FlatTrainer):
         self._out = ops.branch_merge(ys, self.merge_w)
         return self._out
 
-    def _zero_grads(self):
-        # the head's explicit schedule writes its dW; autograd accumulates the rest
-        (self.lstm_grad if self.concat else self.grad).zero_()
-
     def backward(self, dout, stream=None):
         """Every gradient of the last forward from d(out) [N, M, out_features], into
         the (zeroed) bucket.  Merge by weights: autograd from the merge down (ONE
         cg_branch_merge_backward, each branch's filter backward, its BPTT).  Merge
         by concat: the head's explicit schedule, then conv_init's dx through
-        cg_concat_drop_backward as every branch's dh_T.  An input that requires
-        grad gets its ``.grad``."""
-        s = self._stream(stream)
-        self._zero_grads()
+        cg_concat_drop_backward as every branch's dh_T (``LSTMHead``).  An input that
+        requires grad gets its ``.grad``."""
         if self.concat:
-            self.head.backward(dout.contiguous(), s)
-            if self._a is not None and self._a.requires_grad:
-                self._a.backward(self.head.dx_in)
-        elif self._out is not None and self._out.requires_grad:
-            self._out.backward(dout)
-        self._out = self._a = None
-
-    def train_step(self, x, labels, stream=None):
-        """One optimizer step; returns the device loss [1] (this rank's batch)."""
-        s = self._stream(stream)
-        out = self.forward(x, stream)
-        self._loss(out, labels, s)
-        self.backward(self.dout, stream)
-        self._exchange_and_update(s)
-        return self.loss
-
-    def predict(self, data, labels=None, reference_dropout: bool = False):
-        """GraphModel.predict as ``LSTMStackTrainer.predict``: no dropout by default;
-        ``reference_dropout=True`` applies the wrappers' masks as a training forward
-        does (the reference's DropoutWrapper is a constant of its graph)."""
-        return super().predict(data, labels, dropout=reference_dropout)
-
-    def evaluate(self, data, labels, reference_dropout: bool = False):
-        """GraphModel.evaluate (lib/graph_model.py:96-122): (string, mse, 0, loss, predictions)."""
-        return super().evaluate(data, labels, dropout=reference_dropout)
+            return self._head_backward(dout, self._stream(stream))
+        self.grad.zero_()
+        out, self._out = self._out, None
+        if out is not None and out.requires_grad:
+            out.backward(dout)

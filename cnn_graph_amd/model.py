@@ -48,11 +48,9 @@ import math
 import torch
 
 from . import _lib
-from . import filter as _filter
 from . import ops
 from .graph_conv import truncated_normal_
-from .plan import plan_for
-from .trainer import FlatTrainer
+from .trainer import FlatTrainer, is_fourier
 
 
 ACTS = ("relu", "relu", "none")  # residual_network: after conv_init, in the layers, after convN
@@ -70,22 +68,124 @@ def _chain(scope, Fin, F, R, Fout_last, acts=ACTS):
     return layers
 
 
+def head_names(conv_layer_num: int, suffix: str = ""):
+    """The variable names of a gconv network of lib/gconv_lstm.py (:297-400, :431-607)
+    in creation order: conv_init, the residual layers, output_layer; ``suffix``
+    (``_{j}``) marks branch j's scopes."""
+    names = [f"conv_init{suffix}/weights"]
+    for i in range(conv_layer_num):
+        names += [f"conv_layer_{i}{suffix}/residual_layer_{i}/sublayer{k}/weights" for k in (0, 1)]
+    return names + [f"output_layer{suffix}/weights"]
+
+
+class _ChebFilter:
+    """ONE Chebyshev filter of a device model: its forward and backward C-ABI
+    calls and the basis saved between them -- in the planes layout where it
+    applies, else rows (``layout`` overrides the choice).  ``W``, ``dW`` and ``out``
+    are the caller's; the plan and the workspace are the ``owner``'s (a FlatTrainer)."""
+
+    def __init__(self, owner, fi, fo, K, act, W, dW, out, layout=None):
+        N, M, plan = owner.N, owner.M, owner.plan
+        self.o, self.W, self.dW, self.out = owner, W, dW, out
+        self.dims, self.act = (plan.handle, N, fi, K, fo), ops.ACTS[act]
+        if layout is None:
+            layout = "planes" if plan.basis_elems(N, fi, K, fo, "planes") else "rows"
+        self.layout, self._layout = layout, _lib.BASIS_LAYOUTS[layout]
+        self.basis = torch.empty((K, N * M, fi) if layout == "planes" else (N * M, fi * K),
+                                 device=owner.device, dtype=torch.float32)
+        h = _lib.lib()
+        self._fwd, self._bwd = h.cg_cheb_forward_layout, h.cg_cheb_backward_layout
+
+    wshape = staticmethod(lambda fi, fo, K, M: (fi * K, fo))
+
+    def ws_bytes(self):
+        return max(self.o.plan.workspace_bytes(*self.dims[1:]))
+
+    def forward(self, x, res, s):
+        """out = act(filter(x; W) + res)."""
+        o = self.o
+        st = self._fwd(*self.dims, x.data_ptr(), self.W.data_ptr(),
+                       res.data_ptr() if res is not None else None, self.act, self._layout,
+                       self.basis.data_ptr(), self.out.data_ptr(), o.ws.data_ptr(), o.ws_n, s)
+        _lib.check("cg_cheb_forward_layout", st)
+        return self.out
+
+    def backward(self, dy, dz, dx, dx_acc, s):
+        """dW, and where given dz (= dy through the activation) and dx (+= with ``dx_acc``)."""
+        o = self.o
+        st = self._bwd(*self.dims, dy.data_ptr(), self.out.data_ptr(), self.act, self._layout,
+                       self.basis.data_ptr(), self.W.data_ptr(), dx.data_ptr() if dx is not None else None,
+                       int(dx_acc), self.dW.data_ptr(), dz.data_ptr() if dz is not None else None,
+                       o.ws.data_ptr(), o.ws_n, s)
+        _lib.check("cg_cheb_backward_layout", st)
+
+
+class _FourierFilter:
+    """The same unit on the MFMA transforms (cg_fres_forward / cg_fres_backward):
+    weights [M, Fout, Fin] (lib/graph_conv.py:105), the saved tensor is the
+    spectrum xhat, the owner's prepared basis ``gft`` is read at call time; ``K``
+    is ignored.
+
+    ``drop`` = (keep_prob, seed) or None: the filter reads its input through a
+    dropout mask folded into the transforms (cg_fres_forward_drop /
+    cg_fres_backward_drop; its dx is then written, never accumulated)."""
+
+    drop = None
+
+    def __init__(self, owner, fi, fo, K, act, W, dW, out, layout=None):
+        self.o, self.W, self.dW, self.out = owner, W, dW, out
+        self.dims, self.act = (owner.N, owner.M, fi, fo), ops.ACTS[act]
+        self.xhat = torch.empty((owner.N, owner.M, fi), device=owner.device, dtype=torch.float32)
+        h = _lib.lib()
+        self._fwd, self._bwd = h.cg_fres_forward, h.cg_fres_backward
+        self._fwd_drop, self._bwd_drop = h.cg_fres_forward_drop, h.cg_fres_backward_drop
+
+    wshape = staticmethod(lambda fi, fo, K, M: (M, fo, fi))
+
+    def ws_bytes(self):
+        return max(ops.fres_workspace_bytes(*self.dims))
+
+    def forward(self, x, res, s):
+        o = self.o
+        # through the mask: (keep_prob, seed) go in after x
+        fn, drop = (self._fwd_drop, self.drop) if self.drop is not None else (self._fwd, ())
+        st = fn(*self.dims, o.gft.data_ptr(), o.gft.numel(), self.W.data_ptr(), x.data_ptr(), *drop,
+                res.data_ptr() if res is not None else None, self.act, self.xhat.data_ptr(),
+                self.out.data_ptr(), o.ws.data_ptr(), o.ws_n, s)
+        _lib.check(fn.__name__, st)
+        return self.out
+
+    def backward(self, dy, dz, dx, dx_acc, s):
+        o = self.o
+        grads = (dz.data_ptr() if dz is not None else None, dx.data_ptr() if dx is not None else None)
+        if self.drop is not None:  # (keep_prob, seed, dz, dx): dx =, never +=
+            fn, grads = self._bwd_drop, (*self.drop, *grads)
+        else:
+            fn, grads = self._bwd, (*grads, int(dx_acc))
+        st = fn(*self.dims, o.gft.data_ptr(), o.gft.numel(), self.W.data_ptr(), self.xhat.data_ptr(),
+                dy.data_ptr(), self.out.data_ptr(), self.act, *grads, self.dW.data_ptr(),
+                o.ws.data_ptr(), o.ws_n, s)
+        _lib.check(fn.__name__, st)
+
+
 class _ResNet:
     """One ``residual_network`` (lib/graph_conv.py:305-330): conv_init, R
-    residual layers of two filters each, convN, on the Chebyshev filter.  Its
-    weights and gradients are the next views the owner's ``carve`` hands out,
-    drawn ``truncated_normal(0, 0.1)`` from ``gen`` in creation order.
+    residual layers of two filters each, convN: ``filters``, one ``_ChebFilter``
+    each.  Its weights and gradients are the next views the owner's ``carve``
+    hands out, drawn ``truncated_normal(0, 0.1)`` from ``gen`` in creation order.
 
-    What a net reads from its ``owner`` (a FlatTrainer), and nothing else: the
-    batch and graph sizes ``N`` and ``M``, ``device``, the Chebyshev ``plan`` (the
-    prepared basis ``gft`` for the Fourier net), the flat buffers through
-    ``carve``, and the workspace ``ws`` / ``ws_n`` at call time.
+    What a net and its filters read from the ``owner`` (a FlatTrainer), and
+    nothing else: the batch and graph sizes ``N`` and ``M``, ``device``, the
+    Chebyshev ``plan`` (the prepared basis ``gft`` for the Fourier net), the flat
+    buffers through ``carve``, and the workspace ``ws`` / ``ws_n`` at call time.
 
     ``input_grad``: the input is an activation, not data (the network sits
     behind an LSTM, lib/gconv_lstm.py:382-389): conv_init's backward also
     computes dx into ``dx_in`` [N, M, Fin].  ``names`` replaces the variable
     names (same order).  ``acts``: the three activations of ``_chain`` (the
     gconv networks of lib/gconv_lstm.py:297-372 use tanh, and end a branch in ReLU)."""
+
+    Filter = _ChebFilter
 
     def __init__(self, owner, scope: str, Fin: int, nfilter: int, K: int, R: int, Fout_last: int, gen,
                  input_grad: bool = False, names=None, acts=ACTS):
@@ -96,65 +196,40 @@ class _ResNet:
         self.names = list(names) if names is not None else [name for name, *_ in layers]
         if len(self.names) != len(layers):
             raise ValueError(f"{len(layers)} filters, {len(self.names)} names")
-        self.W, self.dW = [], []
-        for name, (_, fi, fo, _) in zip(self.names, layers):
-            w, dw = owner.carve(self._wshape(fi, fo, K, M), name)
+        f32 = dict(device=owner.device, dtype=torch.float32)
+        self.W, self.dW, self.out, self.filters = [], [], [], []
+        for name, (_, fi, fo, act) in zip(self.names, layers):
+            w, dw = owner.carve(self.Filter.wshape(fi, fo, K, M), name)
             truncated_normal_(w, 0.1, gen)
             self.W.append(w)
             self.dW.append(dw)
-        f32 = dict(device=owner.device, dtype=torch.float32)
+            self.out.append(torch.empty((N, M, fo), **f32))  # saved by the forward
+            self.filters.append(self.Filter(owner, fi, fo, K, act, w, dw, self.out[-1]))
         self.input_grad = bool(input_grad)
         self.dx_in = torch.empty((N, M, Fin), **f32) if input_grad else None
-        # activations saved by the forward, gradient work buffers
-        self.out = [torch.empty((N, M, fo), **f32) for _, _, fo, _ in layers]
+        # gradient work buffers
         self.g = [torch.empty((N, M, nfilter), **f32) for _ in range(3)]
         # a last filter with an activation: its dz, of the output's width
         self.dz_last = torch.empty((N, M, Fout_last), **f32) if layers[-1][3] != "none" else None
-        self._setup(f32)
 
-    @staticmethod
-    def _wshape(fi, fo, K, M):
-        return (fi * K, fo)
+    # the filters' saved tensors: the Chebyshev bases and their layouts
+    layout = property(lambda self: [f.layout for f in self.filters])
+    basis = property(lambda self: [f.basis for f in self.filters])
 
     @classmethod
     def sizes(cls, Fin, F, K, M, R, Fout_last):
         """Parameter counts of the filters, in creation order."""
-        return [math.prod(cls._wshape(fi, fo, K, M)) for _, fi, fo, _ in _chain("", Fin, F, R, Fout_last)]
-
-    def _setup(self, f32):
-        """The filter's saved tensors and C entry points: the Chebyshev bases, in
-        the planes layout where it applies, else rows."""
-        o, N, M, K = self.o, self.o.N, self.o.M, self.K
-        self.layout = ["planes" if o.plan.basis_elems(N, fi, K, fo, "planes") else "rows"
-                       for _, fi, fo, _ in self.layers]
-        self.basis = [torch.empty((K, N * M, fi) if lay == "planes" else (N * M, fi * K), **f32)
-                      for (_, fi, _, _), lay in zip(self.layers, self.layout)]
-        h = _lib.lib()
-        self._fwd, self._bwd = h.cg_cheb_forward_layout, h.cg_cheb_backward_layout
+        return [math.prod(cls.Filter.wshape(fi, fo, K, M))
+                for _, fi, fo, _ in _chain("", Fin, F, R, Fout_last)]
 
     def ws_bytes(self):
-        o = self.o
-        return max(max(o.plan.workspace_bytes(o.N, fi, self.K, fo)) for _, fi, fo, _ in self.layers)
+        return max(f.ws_bytes() for f in self.filters)
 
     def _f(self, li, x, res, s):
-        o = self.o
-        _, fi, fo, act = self.layers[li]
-        st = self._fwd(o.plan.handle, o.N, fi, self.K, fo, x.data_ptr(), self.W[li].data_ptr(),
-                       res.data_ptr() if res is not None else None, ops.ACTS[act],
-                       _lib.BASIS_LAYOUTS[self.layout[li]], self.basis[li].data_ptr(),
-                       self.out[li].data_ptr(), o.ws.data_ptr(), o.ws_n, s)
-        _lib.check("cg_cheb_forward_layout", st)
-        return self.out[li]
+        return self.filters[li].forward(x, res, s)
 
     def _b(self, li, dy, dz, dx, dx_acc, s):
-        o = self.o
-        _, fi, fo, act = self.layers[li]
-        st = self._bwd(o.plan.handle, o.N, fi, self.K, fo, dy.data_ptr(), self.out[li].data_ptr(),
-                       ops.ACTS[act], _lib.BASIS_LAYOUTS[self.layout[li]], self.basis[li].data_ptr(),
-                       self.W[li].data_ptr(), dx.data_ptr() if dx is not None else None, int(dx_acc),
-                       self.dW[li].data_ptr(), dz.data_ptr() if dz is not None else None,
-                       o.ws.data_ptr(), o.ws_n, s)
-        _lib.check("cg_cheb_backward_layout", st)
+        self.filters[li].backward(dy, dz, dx, dx_acc, s)
 
     def forward(self, x, s):
         h = self._f(0, x, None, s)
@@ -187,88 +262,88 @@ class _ResNet:
 
 class _FourierResNet(_ResNet):
     """The same network with the Fourier filter: _ResNet's forward / backward
-    schedule over cg_fres_forward / cg_fres_backward.  Weights [M, Fout, Fin]
-    (lib/graph_conv.py:105); the forward saves each filter's spectrum xhat; ``K``
-    is ignored.
+    schedule over ``_FourierFilter``s; the forward saves each filter's spectrum
+    xhat.  ``filters[0].drop`` folds a dropout mask into conv_init's transforms
+    (needs ``input_grad``)."""
 
-    ``drop`` = (keep_prob, seed) or None: conv_init reads its input through a
-    dropout mask folded into the transforms (cg_fres_forward_drop /
-    cg_fres_backward_drop; needs ``input_grad``)."""
-
-    drop = None
-
-    @staticmethod
-    def _wshape(fi, fo, K, M):
-        return (M, fo, fi)
-
-    def _setup(self, f32):
-        self.xhat = [torch.empty((self.o.N, self.o.M, fi), **f32) for _, fi, _, _ in self.layers]
-        h = _lib.lib()
-        self._fwd, self._bwd = h.cg_fres_forward, h.cg_fres_backward
-        self._fwd_drop, self._bwd_drop = h.cg_fres_forward_drop, h.cg_fres_backward_drop
-
-    def ws_bytes(self):
-        o = self.o
-        return max(max(ops.fres_workspace_bytes(o.N, o.M, fi, fo)) for _, fi, fo, _ in self.layers)
-
-    def _f(self, li, x, res, s):
-        o = self.o
-        _, fi, fo, act = self.layers[li]
-        # conv_init alone reads through the mask: (keep_prob, seed) go in after x
-        fn, drop = (self._fwd_drop, self.drop) if li == 0 and self.drop is not None else (self._fwd, ())
-        st = fn(o.N, o.M, fi, fo, o.gft.data_ptr(), o.gft.numel(), self.W[li].data_ptr(), x.data_ptr(),
-                *drop, res.data_ptr() if res is not None else None, ops.ACTS[act],
-                self.xhat[li].data_ptr(), self.out[li].data_ptr(), o.ws.data_ptr(), o.ws_n, s)
-        _lib.check(fn.__name__, st)
-        return self.out[li]
-
-    def _b(self, li, dy, dz, dx, dx_acc, s):
-        o = self.o
-        _, fi, fo, act = self.layers[li]
-        grads = (dz.data_ptr() if dz is not None else None, dx.data_ptr() if dx is not None else None)
-        if li == 0 and self.drop is not None:  # (keep_prob, seed, dz, dx): dx =, never +=
-            fn, grads = self._bwd_drop, (*self.drop, *grads)
-        else:
-            fn, grads = self._bwd, (*grads, int(dx_acc))
-        st = fn(o.N, o.M, fi, fo, o.gft.data_ptr(), o.gft.numel(), self.W[li].data_ptr(),
-                self.xhat[li].data_ptr(), dy.data_ptr(), self.out[li].data_ptr(), ops.ACTS[act],
-                *grads, self.dW[li].data_ptr(), o.ws.data_ptr(), o.ws_n, s)
-        _lib.check(fn.__name__, st)
+    Filter = _FourierFilter
+    layout = basis = None
+    xhat = property(lambda self: [f.xhat for f in self.filters])
 
 
-FILTERS = ("chebyshev5", "fourier")
+def _net_class(fourier: bool):
+    return _FourierResNet if fourier else _ResNet
 
 
-def _net_class(filter):
-    if filter not in FILTERS:
-        raise ValueError(f"filter must be one of {FILTERS}, got {filter!r}")
-    return _FourierResNet if filter == "fourier" else _ResNet
+class _ChannelSplit:
+    """The channel ranges [a, b) of an input [N, M, C] as contiguous tensors: one
+    pre-allocated buffer (``bufs``) and one cg_slice_channels launch per range; a
+    range that is all of x is x itself (buffer None, no launch)."""
+
+    def __init__(self, owner, C, ranges):
+        N, M = owner.N, owner.M
+        self.rows, self.C, self.ranges = N * M, int(C), list(ranges)
+        self.bufs = [torch.empty((N, M, b - a), device=owner.device, dtype=torch.float32)
+                     if (a, b) != (0, self.C) else None for a, b in self.ranges]
+        self._slice = _lib.lib().cg_slice_channels
+
+    def slices(self, x, s):
+        """Yields the ranges of x in turn.  A range's launch is enqueued when it is
+        drawn: a loop that draws one slice per pass keeps slice and consumer in order."""
+        for (a, b), buf in zip(self.ranges, self.bufs):
+            if buf is not None:
+                _lib.check("cg_slice_channels",
+                           self._slice(x.data_ptr(), self.rows, self.C, a, b, buf.data_ptr(), s))
+            yield x if buf is None else buf
+
+
+class LSTMHead:
+    """The LSTM -> head seam, a mixin for a FlatTrainer whose LSTM layers (autograd,
+    carved first) feed a residual gconv network (``head``: a ``_ResNet`` with
+    ``input_grad``, the explicit schedule)."""
+
+    head = _head_in = None
+
+    def _make_head(self, fourier, Fin, width, R, Fout, gen):
+        # truncated_normal(0, 0.1) on the flat views (lib/filter.py:39, :63), after the cells' draws
+        self.lstm_grad = self.grad[:self._off]  # what autograd accumulates into
+        self.head = _net_class(fourier)(self, "", Fin, width, self.K, R, Fout, gen, input_grad=True,
+                                        names=head_names(R))
+        self.head_W, self.head_dW = self.head.W, self.head.dW
+        self._alloc_ws([self.head])
+
+    def _head_forward(self, a, s):
+        """The head's output on ``a``, the end of the autograd part."""
+        self._head_in = a
+        return self.head.forward(a.detach().contiguous(), s)
+
+    def _head_backward(self, dout, s):
+        """The LSTM part of the bucket zeroed, the head's explicit schedule (its dW
+        written into the bucket), then conv_init's dx into autograd, whose layers
+        accumulate into the bucket."""
+        self.lstm_grad.zero_()
+        self.head.backward(dout.contiguous(), s)
+        a, self._head_in = self._head_in, None
+        if a is not None and a.requires_grad:
+            a.backward(self.head.dx_in)
 
 
 class _ResModel(FlatTrainer):
-    """What ResGNN and StackedResGNN share: the graph (a Chebyshev plan, or U
-    prepared once for the transforms) and the flat Adam trainer over ``total``
-    parameters."""
+    """What ResGNN and StackedResGNN share: the graph (``_set_graph``) and the
+    flat Adam trainer over ``total`` parameters."""
 
     def __init__(self, L, N, nfilter, K, nres_layer_count, Fout_last, learning_rate, decay_rate,
                  decay_steps, device, comm, lmax, filter, total):
         super().__init__(total, (int(N), int(L.shape[0]), int(Fout_last)), "adam", learning_rate,
                          decay_rate, decay_steps, device, comm)
         self.filter = filter
-        if filter == "fourier":  # no Chebyshev plan: U, prepared once for the transforms
-            self.plan = None
-            self.M = int(L.shape[0])
-            self.U = _filter.fourier_basis(L, self.device)
-            self.gft = ops.gft_prepare(self.U)
-        else:
-            dev_index = self.device.index if self.device.index is not None else 0
-            self.plan = plan_for(L, lmax=lmax, device=dev_index)
-            self.M = self.plan.M
+        self._set_graph(L, filter == "fourier", lmax)
         self.N, self.nfilter, self.K = int(N), int(nfilter), int(K)
         self.R, self.Fout_last = int(nres_layer_count), int(Fout_last)
 
     def _make_net(self, scope, Fin, gen):
-        return _net_class(self.filter)(self, scope, Fin, self.nfilter, self.K, self.R, self.Fout_last, gen)
+        net = _net_class(self.filter == "fourier")
+        return net(self, scope, Fin, self.nfilter, self.K, self.R, self.Fout_last, gen)
 
 
 class ResGNN(_ResModel):
@@ -279,7 +354,8 @@ class ResGNN(_ResModel):
                  decay_steps: int | None = None, device=None, seed: int = 2017, comm=None,
                  lmax: float = 2, filter: str = "chebyshev5"):
         """filter: "chebyshev5" or "fourier" (K is then ignored, lib/graph_conv.py:103)."""
-        total = sum(_net_class(filter).sizes(Fin, nfilter, K, L.shape[0], nres_layer_count, Fout_last))
+        net = _net_class(is_fourier(filter))
+        total = sum(net.sizes(Fin, nfilter, K, L.shape[0], nres_layer_count, Fout_last))
         super().__init__(L, N, nfilter, K, nres_layer_count, Fout_last, learning_rate, decay_rate,
                          decay_steps, device, comm, lmax, filter, total)
         self.Fin = int(Fin)
@@ -300,14 +376,9 @@ class ResGNN(_ResModel):
             raise ValueError(f"x must be a cuda tensor of shape {(self.N, self.M, self.Fin)}")
         return self.net.forward(x.contiguous(), s)
 
-    def train_step(self, x, labels, stream=None):
-        """One optimizer step (lib/graph_model.py:277-310); returns the device loss [1]."""
-        s = self._stream(stream)
-        out = self.forward(x, s)
-        self._loss(out, labels, s)
-        self.net.backward(self.dout, s)
-        self._exchange_and_update(s)
-        return self.loss
+    def backward(self, dout, stream=None):
+        """Every dW of the last forward from d(out)."""
+        self.net.backward(dout, self._stream(stream))
 
 
 class StackedResGNN(_ResModel):
@@ -325,7 +396,7 @@ class StackedResGNN(_ResModel):
                  decay_rate: float = 0.95, decay_steps: int | None = None, device=None,
                  seed: int = 2017, comm=None, lmax: float = 2, filter: str = "chebyshev5"):
         """filter: "chebyshev5" or "fourier" (K is then ignored, lib/graph_conv.py:103)."""
-        net = _net_class(filter)
+        net = _net_class(is_fourier(filter))
         groups = [(int(a), int(b)) for a, b in groups]
         if len(groups) < 1 or any(not (0 <= a < b <= C) for a, b in groups):
             raise ValueError(f"bad channel groups {groups} for C={C}")
@@ -347,14 +418,12 @@ class StackedResGNN(_ResModel):
             self.merge_dW.append(dw)
         self._carved()
         self.W, self.dW = self._tensors, self._grads
-        self.x_groups = [torch.empty((self.N, self.M, b - a), **f32) if (a, b) != (0, self.C) else None
-                         for a, b in groups]
+        self.split = _ChannelSplit(self, self.C, groups)
         self.X = torch.empty((self.N, self.M, self.Fout_last), **f32)
         self.d_net = torch.empty((self.N, self.M, self.Fout_last), **f32)
         self._alloc_ws(self.nets)
         h = _lib.lib()
-        self._slice, self._merge_f, self._merge_b = (h.cg_slice_channels, h.cg_stack_merge_forward,
-                                                     h.cg_stack_merge_backward)
+        self._merge_f, self._merge_b = h.cg_stack_merge_forward, h.cg_stack_merge_backward
 
     def forward(self, x, stream=None):
         """_inference (lib/graph_conv.py:274-303): returns X [N, M, Fout_last]."""
@@ -363,30 +432,20 @@ class StackedResGNN(_ResModel):
             raise ValueError(f"x must be a cuda tensor of shape {(self.N, self.M, self.C)}")
         x = x.contiguous()
         N, M, F = self.N, self.M, self.Fout_last
-        for i, ((a, b), net) in enumerate(zip(self.groups, self.nets)):
-            xi = x
-            if self.x_groups[i] is not None:
-                xi = self.x_groups[i]
-                _lib.check("cg_slice_channels",
-                           self._slice(x.data_ptr(), N * M, self.C, a, b, xi.data_ptr(), s))
+        for i, (net, xi) in enumerate(zip(self.nets, self.split.slices(x, s))):
             out = net.forward(xi, s)
             _lib.check("cg_stack_merge_forward",
                        self._merge_f(N, M, F, out.data_ptr(), self.merge_W[i].data_ptr(), int(i > 0),
                                      self.X.data_ptr(), s))
         return self.X
 
-    def train_step(self, x, labels, stream=None):
-        """One optimizer step over every network and merge weight; returns the device loss [1]."""
+    def backward(self, dout, stream=None):
+        """Every network's and merge weight's gradient of the last forward from d(X)."""
         s = self._stream(stream)
-        X = self.forward(x, s)
-        self._loss(X, labels, s)
         N, M, F = self.N, self.M, self.Fout_last
         for i, net in enumerate(self.nets):
-            out = net.out[-1]
             _lib.check("cg_stack_merge_backward",
-                       self._merge_b(N, M, F, self.dout.data_ptr(), out.data_ptr(),
+                       self._merge_b(N, M, F, dout.data_ptr(), net.out[-1].data_ptr(),
                                      self.merge_W[i].data_ptr(), self.d_net.data_ptr(),
                                      self.merge_dW[i].data_ptr(), s))
             net.backward(self.d_net, s)
-        self._exchange_and_update(s)
-        return self.loss

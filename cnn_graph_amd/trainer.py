@@ -1,26 +1,40 @@
-"""``FlatTrainer``: what the device models (``ResGNN``, ``StackedResGNN``,
-``GLSTMModel``, ``GLSTMGconvModel``, ``GLSTMPeriodModel``) share around their forward and backward
-passes (lib/graph_model.py:246-310; sgd / rmsprop of lib/gconvRNN.py:381-389).
+"""``FlatTrainer``: what the seven device models (``ResGNN``, ``StackedResGNN``,
+``GLSTMModel``, ``GLSTMGconvModel``, ``GLSTMPeriodModel``, ``GConvRNNModel``,
+``GConvNetModel``) share around their forward and backward passes
+(lib/graph_model.py:246-310; sgd / rmsprop of lib/gconvRNN.py:381-389).
 
   buffers   every parameter is a view into ONE flat fp32 buffer (``flat``),
             every gradient a view into ONE flat bucket (``grad``); the optimizer
             slots ``s1`` / ``s2`` have the same size.  ``carve`` hands the views
             out in creation order and records their names.
+  graph     ``_set_graph`` / ``_graph_from_cell``: a Chebyshev ``plan``, or ``U`` and
+            its prepared transform ``gft``; ``is_fourier`` / ``is_fourier_conv``
+            validate the two filter vocabularies
+  step      ``train_step``: forward, loss, backward, exchange, update
   loss      mean((labels - out)^2), dout and the loss moving average
             (lib/graph_model.py:265-273)                       cg_mse_loss_ema
   exchange  ONE all-reduce(sum) of the bucket when ``comm.world`` > 1
   update    ONE optimizer launch over ``flat``, grad_scale = 1/world
             (``_grad_scale``), at the staircase exponentially decayed learning
             rate; ``_after_exchange`` runs between exchange and update
-  predict / evaluate  GraphModel's (lib/graph_model.py:64-122) through evaluate.py
+  predict / evaluate  GraphModel's (lib/graph_model.py:64-122) through evaluate.py;
+            ``DropoutEval`` adds ``reference_dropout`` for the models with wrappers
   fit       GraphModel.fit (lib/graph_model.py:124-197): the dataset lives on the
             device, ``fit_schedule`` restates the reference's index deque on the
             host, and each step is ONE cg_batch_gather plus ``train_step``
 
 A model derives from it, allocates with ``FlatTrainer.__init__``, carves its
-parameters, calls ``_carved()`` and implements ``forward``.  ``comm`` is any
-object with ``allreduce_sum_(tensor, stream)`` and ``world`` (``dist.RcclComm``
-on RCCL, ``dist.TorchComm`` on a process group).
+parameters, calls ``_carved()`` and implements two hooks:
+
+  forward(x, stream=None, ...)   the output [N, M, Fout]; keeps what backward needs
+  backward(dout, stream)         every gradient of the last forward into the bucket,
+                                 zeroing first the part autograd ACCUMULATES into
+
+and, where the defaults do not fit, ``_grad_scale`` and ``_after_exchange``
+(``GConvRNNModel``, which also has a ``train_step`` of its own: its loss is not
+the mean squared error).  ``comm`` is any object with ``allreduce_sum_(tensor,
+stream)`` and ``world`` (``dist.RcclComm`` on RCCL, ``dist.TorchComm`` on a
+process group).
 """
 from __future__ import annotations
 
@@ -33,9 +47,38 @@ import torch
 
 from . import _lib
 from . import evaluate as _ev
+from . import filter as _filter
 from . import ops
+from .plan import plan_for
 
 OPTIMIZERS = ("adam", "sgd", "rmsprop")
+FILTERS = ("chebyshev5", "fourier")  # lib/graph_conv.py's names: ResGNN, StackedResGNN
+
+
+def is_fourier(filter) -> bool:
+    """Validates a ``FILTERS`` name; True for the Fourier filter."""
+    if filter not in FILTERS:
+        raise ValueError(f"filter must be one of {FILTERS}, got {filter!r}")
+    return filter == "fourier"
+
+
+def is_fourier_conv(filter) -> bool:
+    """Validates one of lib/filter.py's names; True for the Fourier filter."""
+    if filter not in ("cheby_conv", "fourier_conv"):
+        raise ValueError("filter must be 'cheby_conv' or 'fourier_conv'")
+    return filter == "fourier_conv"
+
+
+def check_keep_prob(keep_prob, name: str = "keep_prob") -> float:
+    if not 0.0 < float(keep_prob) <= 1.0:
+        raise ValueError(f"{name} must be in (0, 1], got {keep_prob}")
+    return float(keep_prob)
+
+
+def check_seam(seam) -> str:
+    if seam not in ("auto", "fused", "unfused"):
+        raise ValueError("seam must be 'auto', 'fused' or 'unfused'")
+    return seam
 
 
 def fit_schedule(S: int, batch: int, num_steps: int, rng=None) -> np.ndarray:
@@ -71,8 +114,6 @@ def fit_schedule(S: int, batch: int, num_steps: int, rng=None) -> np.ndarray:
 
 
 class FlatTrainer:
-    OPTIMIZERS = OPTIMIZERS
-
     def __init__(self, total: int, out_shape, optimizer: str, learning_rate, decay_rate, decay_steps,
                  device, comm):
         """total: the parameter count; out_shape: (N, M, Fout) of the model's output."""
@@ -136,6 +177,30 @@ class FlatTrainer:
 
     def _carved(self):
         assert self._off == self.flat.numel(), (self._off, self.flat.numel())
+
+    # -- the graph ------------------------------------------------------------------
+    def _set_graph(self, L, fourier: bool, lmax):
+        """``M`` and a Chebyshev ``plan``, or -- no plan -- ``U`` and ``gft``, U prepared once."""
+        self.plan = self.U = self.gft = None
+        if fourier:
+            self.M = int(L.shape[0])
+            self.U = _filter.fourier_basis(L, self.device)
+            self.gft = ops.gft_prepare(self.U)
+        else:
+            dev_index = self.device.index if self.device.index is not None else 0
+            self.plan = plan_for(L, lmax=lmax, device=dev_index)
+            self.M = self.plan.M
+
+    def _graph_from_cell(self, cell, gft: bool = False):
+        """The same from a model's first LSTM cell.  ``gft``: a residual head will
+        read the prepared transform -- the fused cell's own, else prepared here."""
+        fourier = cell.filter_type == "fourier_conv"
+        self.M = cell._nNode
+        self.plan = None if fourier else cell.plan
+        self.U = cell.U if fourier else None
+        self.gft = None
+        if fourier and gft:
+            self.gft = cell.gft_basis if cell.gft_basis is not None else ops.gft_prepare(self.U)
 
     def _alloc_ws(self, nets):
         # one workspace serves every forward and backward call of the nets (stream
@@ -214,6 +279,16 @@ class FlatTrainer:
                               f(0.0), f(1e-10), scale, s)
         _lib.check(f"cg_{self.optimizer}_update", st)
 
+    def train_step(self, x, labels, stream=None):
+        """One optimizer step (lib/graph_model.py:277-310) on this rank's batch;
+        returns the device loss [1]."""
+        s = self._stream(stream)
+        out = self.forward(x, stream=s)
+        self._loss(out, labels, s)
+        self.backward(self.dout, s)
+        self._exchange_and_update(s)
+        return self.loss
+
     # -- inference ------------------------------------------------------------------
     def predict(self, data, labels=None, **forward_kw):
         """GraphModel.predict (lib/graph_model.py:64-94): predictions [size, M,
@@ -228,7 +303,7 @@ class FlatTrainer:
         """GraphModel.evaluate (:96-122): (string, mse, 0, loss, predictions)."""
         return _ev.evaluate(lambda d, l: FlatTrainer.predict(self, d, l, **forward_kw), data, labels)
 
-    # -- training -------------------------------------------------------------------
+    # -- training loop --------------------------------------------------------------
     def fit(self, train_data, train_labels, val_data, val_labels, num_epochs=20, eval_frequency=200,
             rng=None, verbose=True, stream=None, rank=None):
         """GraphModel.fit (lib/graph_model.py:124-197): ``int(num_epochs * S / B)``
@@ -314,3 +389,20 @@ class FlatTrainer:
             print("validation accuracy: peak = {:.2f}, mean = {:.2f}".format(max(accuracies),
                                                                             np.mean(accuracies[-10:])))
         return accuracies, losses, (time.time() - t_wall) / num_steps
+
+
+class DropoutEval:
+    """``predict`` / ``evaluate`` of a model whose ``forward`` takes ``dropout``
+    (DropoutWrappers inside); goes in front of FlatTrainer in the bases."""
+
+    def predict(self, data, labels=None, reference_dropout: bool = False):
+        """``FlatTrainer.predict``.  Dropout at evaluation: the reference's DropoutWrapper(0.8) is a constant
+        of its graph, so the reference ALSO drops when it evaluates.  The
+        default here is no dropout (deterministic predictions);
+        ``reference_dropout=True`` applies the wrappers' masks as a training
+        forward does (and advances their mask streams)."""
+        return super().predict(data, labels, dropout=reference_dropout)
+
+    def evaluate(self, data, labels, reference_dropout: bool = False):
+        """``FlatTrainer.evaluate``; ``reference_dropout`` as in ``predict``."""
+        return super().evaluate(data, labels, dropout=reference_dropout)

@@ -13,11 +13,19 @@ the commit BEFORE the four models moved onto ``trainer.FlatTrainer`` computed
 them.  ``test_models_unchanged`` replays them.  It was recorded twice, in two
 processes, and the two files were identical.
 
+branch_model_steps.npz (``--branch-models``): the same for ``BRANCH_CASES`` --
+``GLSTMPeriodModel``, ``GConvNetModel`` (both on the eight channels of
+``branch_case``, T = (2, 1, 1)) and ``GConvRNNModel`` (x [N, M, F, T], integer
+labels [N, T]; flat and loss, it has no loss average) -- as the commit BEFORE the
+models' shared pieces moved into ``trainer.py`` computed them.  Recorded twice,
+in two processes; the two files were identical.
+
 How they were generated: with the parent commit's package (its Python files and
 its built libcheb_mi355.so) first on PYTHONPATH,
 
     PYTHONPATH=<parent checkout> python tests/golden/make_resgnn_steps.py OUT.npz
     PYTHONPATH=<parent checkout> python tests/golden/make_resgnn_steps.py --models OUT.npz
+    PYTHONPATH=<parent checkout> python tests/golden/make_resgnn_steps.py --branch-models OUT.npz
 
 The inputs come from ``resgnn_case`` / ``model_case`` below, which the tests
 import, so both sides draw the same numbers.  Needs a GPU; not run by the suite.
@@ -52,6 +60,36 @@ MODEL_CASES = {
     "glstm_gconv_fourier_fused": ("GLSTMGconvModel", dict(filter="fourier_conv", seam="fused", **_HEAD)),
     "glstm_gconv_cheby": ("GLSTMGconvModel", dict(filter="cheby_conv", **_HEAD)),
 }
+# the branch models read C = 8 columns: T = (2, 1, 1) windows of F = 2 flows
+BRANCH_T = (2, 1, 1)
+_PERIOD = dict(T=BRANCH_T, feat_in=2, num_hidden=8, K=2, conv_layer_num=1, **_LSTM)
+_NET = dict(T=BRANCH_T, num_hidden=8, K=2, conv_layer_num=1)
+_RNN = dict(num_hidden=8, K=3, keep_prob=0.8)
+BRANCH_CASES = {
+    "period_expand_cheby": ("GLSTMPeriodModel", dict(infer_func="inference_glstm_period_expand",
+                                                     filter="cheby_conv", **_PERIOD)),
+    "period_expand_fourier": ("GLSTMPeriodModel", dict(infer_func="inference_glstm_period_expand",
+                                                       filter="fourier_conv", **_PERIOD)),
+    "period_gconv1_cheby": ("GLSTMPeriodModel", dict(infer_func="inference_glstm_period_expand_gconv1",
+                                                     filter="cheby_conv", **_PERIOD)),
+    "period_gconv3_cheby": ("GLSTMPeriodModel", dict(infer_func="inference_glstm_period_expand_gconv3",
+                                                     filter="cheby_conv", **_PERIOD)),
+    "period_gconv3_fourier": ("GLSTMPeriodModel", dict(infer_func="inference_glstm_period_expand_gconv3",
+                                                       filter="fourier_conv", **_PERIOD)),
+    "period_split_cheby": ("GLSTMPeriodModel", dict(infer_func="inference_glstm_gconv_split",
+                                                    filter="cheby_conv", **_PERIOD)),
+    "gconv_cheby": ("GConvNetModel", dict(infer_func="inference_gconv", filter="cheby_conv", **_NET)),
+    "gconv_expand_cheby": ("GConvNetModel", dict(infer_func="inference_gconv_period_expand",
+                                                 filter="cheby_conv", **_NET)),
+    "gconv_no_expand_cheby": ("GConvNetModel", dict(infer_func="inference_gconv_period_no_expand",
+                                                    filter="cheby_conv", **_NET)),
+    "gconv_no_expand_fourier": ("GConvNetModel", dict(infer_func="inference_gconv_period_no_expand",
+                                                      filter="fourier_conv", **_NET)),
+    "rnn_fused_clip": ("GConvRNNModel", dict(seam="fused", max_grad_norm=0.05, **_RNN)),
+    "rnn_unfused_clip": ("GConvRNNModel", dict(seam="unfused", max_grad_norm=0.05, **_RNN)),
+    "rnn_adam": ("GConvRNNModel", dict(optimizer="adam", **_RNN)),
+}
+MODEL_CASES.update(BRANCH_CASES)
 
 
 def resgnn_case():
@@ -75,6 +113,19 @@ def model_case():
     x = (0.5 * rng.standard_normal((c["N"], c["M"], c["F"] * c["T"]))).astype(np.float32)
     labels = rng.standard_normal((c["N"], c["M"], c["Fout"])).astype(np.float32)
     return GR.ring_chords_laplacian(c["M"]), x, labels
+
+
+@functools.lru_cache(maxsize=None)
+def branch_case():
+    """(x [N, M, 8], labels [N, M, Fout], x_seq [N, M, F, T], vertex labels [N, T]
+    int64) of BRANCH_CASES, on ``model_case``'s Laplacian."""
+    c = MODEL
+    rng = np.random.default_rng(2026)
+    x = (0.5 * rng.standard_normal((c["N"], c["M"], c["F"] * sum(BRANCH_T)))).astype(np.float32)
+    labels = rng.standard_normal((c["N"], c["M"], c["Fout"])).astype(np.float32)
+    x_seq = (0.5 * rng.standard_normal((c["N"], c["M"], c["F"], c["T"]))).astype(np.float32)
+    vertices = rng.integers(0, c["M"], size=(c["N"], c["T"]), dtype=np.int64)
+    return x, labels, x_seq, vertices
 
 
 def run_steps(filter):
@@ -102,6 +153,15 @@ def build_model(name, dev):
     cls, kw = MODEL_CASES[name]
     common = dict(decay_steps=c["decay_steps"], decay_rate=c["decay_rate"], device=dev, seed=c["seed"])
     L = model_case()[0]
+    if cls == "GLSTMPeriodModel":
+        from cnn_graph_amd.glstm_period import GLSTMPeriodModel
+        return GLSTMPeriodModel(L, c["N"], out_features=c["Fout"], **common, **kw)
+    if cls == "GConvNetModel":
+        from cnn_graph_amd.gconv_net import GConvNetModel
+        return GConvNetModel(L, c["N"], out_features=c["Fout"], **common, **kw)
+    if cls == "GConvRNNModel":  # a constant learning rate: no decay to set
+        from cnn_graph_amd.gconv_rnn import GConvRNNModel
+        return GConvRNNModel(L, c["N"], c["T"], c["F"], device=dev, seed=c["seed"], **kw)
     if cls == "StackedResGNN":
         return StackedResGNN(L, c["N"], c["F"] * c["T"], c["C"], 3, 1, groups=((0, 4), (4, 6)),
                              Fout_last=c["Fout"], **common, **kw)
@@ -110,11 +170,17 @@ def build_model(name, dev):
 
 
 def run_model_steps(name):
-    """(flat, loss, ema) after MODEL['steps'] steps of a fresh MODEL_CASES[name]."""
+    """(flat, loss, ema) after MODEL['steps'] steps of a fresh MODEL_CASES[name]
+    (GConvRNNModel's loss is not FlatTrainer's: its ema stays zero)."""
     import torch
     dev = torch.device("cuda", 0)
     m = build_model(name, dev)
-    _, x, labels = model_case()
+    if name not in BRANCH_CASES:
+        _, x, labels = model_case()
+    elif MODEL_CASES[name][0] == "GConvRNNModel":
+        x, labels = branch_case()[2:]
+    else:
+        x, labels = branch_case()[:2]
     xt, lt = torch.from_numpy(x).to(dev), torch.from_numpy(labels).to(dev)
     for _ in range(MODEL["steps"]):
         loss = m.train_step(xt, lt)
@@ -125,8 +191,10 @@ def run_model_steps(name):
 
 if __name__ == "__main__":
     out = {}
-    if sys.argv[1] == "--models":
+    if sys.argv[1] in ("--models", "--branch-models"):
         for name in MODEL_CASES:
+            if (name in BRANCH_CASES) != (sys.argv[1] == "--branch-models"):
+                continue
             out[f"{name}_flat"], out[f"{name}_loss"], out[f"{name}_ema"] = run_model_steps(name)
     else:
         for f in ("chebyshev5", "fourier"):
