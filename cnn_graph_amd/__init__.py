@@ -16,11 +16,12 @@ Modules
   dist        one-process-per-GPU data parallelism (RCCL all-reduce)
   glstm_period  GLSTMPeriodModel: the closeness / period / trend gconv-LSTM networks
   gconv_net   GConvNetModel: the pure graph-convolution networks (inference_gconv*)
+  cgcnn       CGCNNModel: the pooled cgcnn classifier (lib/models.py), trained on device
 """
 __version__ = "0.1.0"
 
 __all__ = ["graph", "plan", "ops", "graph_conv", "filter", "coarsening", "dist", "GLSTMPeriodModel",
-           "GConvNetModel"]
+           "GConvNetModel", "CGCNNModel"]
 
 
 def __getattr__(name):
@@ -31,4 +32,7 @@ def __getattr__(name):
     if name == "GConvNetModel":
         from .gconv_net import GConvNetModel
         return GConvNetModel
+    if name == "CGCNNModel":
+        from .cgcnn import CGCNNModel
+        return CGCNNModel
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -150,6 +150,9 @@ _SIGNATURES = {
     "cg_seq_xent_head": ([_vp, _vp, _vp, _vp, _c_i32, _c_i32, _c_i32, _c_i32, ctypes.c_float,
                           ctypes.c_uint64, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_sz,
                           _vp], _c_int),
+    "cg_class_xent_workspace_bytes": ([_c_i32, _c_i32, _c_i64, ctypes.POINTER(_c_sz)], _c_int),
+    "cg_class_xent_ema": ([_vp, _vp, _c_i32, _c_i32, _vp, _c_i64, _c_i64, ctypes.c_float, _vp, _vp,
+                           _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _c_sz, _vp], _c_int),
     # the branch seams: host arrays of B device pointers / sizes / seeds
     "cg_branch_merge_forward": ([_c_i32, _c_i32, _c_i32, _c_i32, _pp, _pp, _vp, _vp], _c_int),
     "cg_branch_merge_backward": ([_c_i32, _c_i32, _c_i32, _c_i32, _vp, _pp, _pp, _pp, _pp, _c_i32,
@@ -178,6 +181,8 @@ _SIGNATURES = {
     "cg_sgd_update": ([_vp, _vp, _c_i64, ctypes.c_float, ctypes.c_float, _vp], _c_int),
     "cg_rmsprop_update": ([_vp, _vp, _vp, _vp, _c_i64, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                            ctypes.c_float, ctypes.c_float, _vp], _c_int),
+    "cg_momentum_update": ([_vp, _vp, _vp, _c_i64, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                            ctypes.c_float, _c_i64, _c_i64, _vp], _c_int),
     "cg_comm_unique_id": ([ctypes.c_char_p], _c_int),
     "cg_comm_init": ([ctypes.POINTER(_vp), _c_int, _c_int, ctypes.c_char_p, _c_int], _c_int),
     "cg_allreduce_sum_f32": ([_vp, _vp, _c_sz, _vp], _c_int),

@@ -470,6 +470,16 @@ hipError_t launch_seq_xent(const float* hs, const float* w, const float* b, cons
                            float loss_scale, float* logits, float* ce, float* loss, float* dhs,
                            float* dw, float* db, float* ws, hipStream_t s);
 
+// ---- class softmax cross-entropy + L2 term + moving average (class_xent.hip) ------
+// logits [N][C], labels [N]; reg: the first of reg_n regularised parameters
+// (reg_n == 0: none); ws: class_xent_ws_bytes.  dlogits, ema, pred, correct and
+// status are nullable.
+size_t class_xent_ws_bytes(int N, int64_t reg_n);
+hipError_t launch_class_xent(const float* logits, const int32_t* labels, int N, int C,
+                             const float* reg, int64_t reg_n, float reg_scale, float* loss,
+                             float* dlogits, float* ema, float decay, int32_t* pred,
+                             int32_t* correct, int32_t* status, float* ws, hipStream_t s);
+
 // ---- gconv-LSTM cell (lstm.hip) ------------------------------------------------
 // gates: 0 = reference gate functions (tan / sigmoid / sigmoid / tanh,
 // lib/gconv_lstm.py:188-209), 1 = standard LSTM (tanh / ... / sigmoid).
@@ -597,6 +607,11 @@ hipError_t launch_rmsprop(float* param, const float* grad, float* ms, float* mom
                           float rho, float momentum, float eps, float grad_scale, hipStream_t s);
 hipError_t launch_adam(float* param, const float* grad, float* m, float* v, int64_t n, float lr_t,
                        float beta1, float beta2, float eps, float grad_scale, hipStream_t s);
+// TF 1.x Momentum (momentum == 0: gradient descent, accum unused) with reg * p
+// added to the gradient of the elements [reg_begin, reg_begin + reg_n)
+hipError_t launch_momentum(float* param, const float* grad, float* accum, int64_t n, float lr,
+                           float momentum, float grad_scale, float reg, int64_t reg_begin,
+                           int64_t reg_n, hipStream_t s);
 // tf.nn.dropout's mask draw, the single definition k_dropout / k_dropout4 and
 // k_gft's dropout modes share, so all agree bitwise.
 // U[0, 1) of element i under `seed` (splitmix64 finaliser of a Weyl sequence;

@@ -201,6 +201,60 @@ __global__ __launch_bounds__(256) void k_rmsprop(float* __restrict__ param,
   }
 }
 
+// The cgcnn classifier's update (lib/models.py:24-55: MomentumOptimizer, or
+// GradientDescent when momentum == 0; TF 1.x ApplyMomentum without Nesterov),
+// with the L2 term of the regularised variables [rb, rb + rn) added to the
+// exchanged gradient:
+//   g = grad * grad_scale (+ reg * p inside the range)
+//   momentum != 0:  accum = accum * momentum + g;  p -= lr * accum
+//   momentum == 0:  p -= g * lr                    (k_sgd's arithmetic; accum unused)
+__device__ __forceinline__ float momentum_elem(float p, float grad, float& acc, int64_t i,
+                                               float lr, float momentum, float grad_scale,
+                                               float reg, int64_t rb, int64_t re) {
+#pragma clang fp contract(off)
+  float g = grad * grad_scale;
+  if (i >= rb && i < re) g = g + reg * p;
+  if (momentum == 0.f) return p - g * lr;
+  acc = acc * momentum + g;
+  return p - lr * acc;
+}
+
+// V4: param, grad and accum are 16-byte aligned -- n / 4 float4 lanes (the
+// regularised range is tested per element, so it needs no alignment), then the
+// n % 4 tail by the first threads; else one element per lane.
+template <bool V4>
+__global__ __launch_bounds__(256) void k_momentum(float* __restrict__ param,
+                                                  const float* __restrict__ grad,
+                                                  float* __restrict__ accum, int64_t n, float lr,
+                                                  float momentum, float grad_scale, float reg,
+                                                  int64_t rb, int64_t re) {
+  const bool mom = momentum != 0.f;
+  const int64_t t0 = int64_t(blockIdx.x) * 256 + threadIdx.x, stride = int64_t(gridDim.x) * 256;
+  int64_t done = 0;
+  if (V4) {
+    const int64_t n4 = n >> 2;
+    float4* p4 = reinterpret_cast<float4*>(param);
+    const float4* g4 = reinterpret_cast<const float4*>(grad);
+    float4* a4 = reinterpret_cast<float4*>(accum);
+    for (int64_t q = t0; q < n4; q += stride) {
+      float4 p = p4[q], a = mom ? a4[q] : make_float4(0.f, 0.f, 0.f, 0.f);
+      const float4 g = g4[q];
+      p.x = momentum_elem(p.x, g.x, a.x, 4 * q, lr, momentum, grad_scale, reg, rb, re);
+      p.y = momentum_elem(p.y, g.y, a.y, 4 * q + 1, lr, momentum, grad_scale, reg, rb, re);
+      p.z = momentum_elem(p.z, g.z, a.z, 4 * q + 2, lr, momentum, grad_scale, reg, rb, re);
+      p.w = momentum_elem(p.w, g.w, a.w, 4 * q + 3, lr, momentum, grad_scale, reg, rb, re);
+      p4[q] = p;
+      if (mom) a4[q] = a;
+    }
+    done = 4 * n4;
+  }
+  for (int64_t i = done + t0; i < n; i += stride) {
+    float a = mom ? accum[i] : 0.f;
+    param[i] = momentum_elem(param[i], grad[i], a, i, lr, momentum, grad_scale, reg, rb, re);
+    if (mom) accum[i] = a;
+  }
+}
+
 // Slab reduction + Adam for a step with no exchange between them (one GPU):
 // the summation is k_reduce_slabs' (wave w sums slabs w, w+16, ..., then the 16
 // partials in wave order), so grad is bitwise the unfused dW; wave 0 then
@@ -330,6 +384,21 @@ hipError_t launch_rmsprop(float* param, const float* grad, float* ms, float* mom
                           float rho, float momentum, float eps, float grad_scale, hipStream_t s) {
   hipLaunchKernelGGL(k_rmsprop, dim3(grid_for(n, 256)), dim3(256), 0, s, param, grad, ms, mom, n, lr,
                      rho, momentum, eps, grad_scale);
+  return hipGetLastError();
+}
+
+hipError_t launch_momentum(float* param, const float* grad, float* accum, int64_t n, float lr,
+                           float momentum, float grad_scale, float reg, int64_t reg_begin,
+                           int64_t reg_n, hipStream_t s) {
+  const bool v4 = n >= 4 && ((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) |
+                              reinterpret_cast<uintptr_t>(accum)) & 15) == 0;
+  const int64_t re = reg_begin + reg_n;
+  if (v4)
+    hipLaunchKernelGGL(k_momentum<true>, dim3(grid_for((n + 3) / 4, 256)), dim3(256), 0, s, param,
+                       grad, accum, n, lr, momentum, grad_scale, reg, reg_begin, re);
+  else
+    hipLaunchKernelGGL(k_momentum<false>, dim3(grid_for(n, 256)), dim3(256), 0, s, param, grad,
+                       accum, n, lr, momentum, grad_scale, reg, reg_begin, re);
   return hipGetLastError();
 }
 

@@ -1,5 +1,5 @@
 // C ABI of the training ops (see include/cheb_mi355.h): loss, dropout, clip,
-// seq_xent, slice and stack, weight and bias gradients, bias_act, gemm, pooling,
+// seq_xent, class_xent, slice and stack, weight and bias gradients, bias_act, gemm, pooling,
 // perm, the batch gather and the optimizers -- argument validation and the launches.
 #include "../../include/cheb_mi355.h"
 
@@ -91,6 +91,37 @@ int cg_seq_xent_head(const float* hs, const float* w, const float* b, const int3
   CG_HIP(cg::launch_seq_xent(hs, w, b, labels, T, N, M, H, keep, seed, loss_scale, logits, ce, loss,
                              dhs, dw, db, static_cast<float*>(ws),
                              reinterpret_cast<hipStream_t>(stream)));
+  return ok();
+}
+
+int cg_class_xent_workspace_bytes(int32_t N, int32_t C, int64_t reg_n, size_t* bytes) {
+  if (!bytes || N < 1 || C < 1 || reg_n < 0)
+    return fail(CG_ERR_ARG, "class_xent_workspace_bytes: bad arguments");
+  if (int rc = cg::below_2_31("class_xent: logits", N, C)) return rc;
+  *bytes = al256(cg::class_xent_ws_bytes(N, reg_n));
+  return ok();
+}
+
+int cg_class_xent_ema(const float* logits, const int32_t* labels, int32_t N, int32_t C,
+                      const float* params, int64_t reg_begin, int64_t reg_n, float reg_scale,
+                      float* loss, float* dlogits, float* ema, float decay, int32_t* pred,
+                      int32_t* correct, int32_t* status, void* workspace, size_t ws_bytes,
+                      void* stream) {
+  if (!logits || !labels || !loss) return fail(CG_ERR_ARG, "class_xent_ema: null pointer");
+  if (N < 1 || C < 1) return fail(CG_ERR_ARG, "class_xent_ema: bad sizes (N=%d C=%d)", N, C);
+  if (int rc = cg::below_2_31("class_xent_ema: logits", N, C)) return rc;
+  if (reg_begin < 0 || reg_n < 0 || (reg_n > 0 && !params))
+    return fail(CG_ERR_ARG, "class_xent_ema: bad regularised range [%lld, +%lld)",
+                (long long)reg_begin, (long long)reg_n);
+  if (ema && !(decay >= 0.f && decay <= 1.f))
+    return fail(CG_ERR_ARG, "class_xent_ema: decay = %g outside [0, 1]", decay);
+  if (int rc = cg::no_alias("class_xent_ema: dlogits", {dlogits}, {logits})) return rc;
+  if (int rc = need_ws("class_xent_ema", workspace, ws_bytes, al256(cg::class_xent_ws_bytes(N, reg_n))))
+    return rc;
+  CG_HIP(cg::launch_class_xent(logits, labels, N, C, reg_n > 0 ? params + reg_begin : nullptr, reg_n,
+                               reg_scale, loss, dlogits, ema, decay, pred, correct, status,
+                               static_cast<float*>(workspace),
+                               reinterpret_cast<hipStream_t>(stream)));
   return ok();
 }
 
@@ -313,6 +344,22 @@ int cg_sgd_update(float* param, const float* grad, int64_t n, float lr, float gr
   if (!param || !grad || n < 0) return fail(CG_ERR_ARG, "sgd_update: bad arguments");
   if (n == 0) return ok();
   CG_HIP(cg::launch_sgd(param, grad, n, lr, grad_scale, reinterpret_cast<hipStream_t>(stream)));
+  return ok();
+}
+
+int cg_momentum_update(float* param, const float* grad, float* accum, int64_t n, float lr,
+                       float momentum, float grad_scale, float reg, int64_t reg_begin,
+                       int64_t reg_n, void* stream) {
+  if (!param || !grad || n < 0 || !(momentum >= 0.f) || (momentum != 0.f && !accum))
+    return fail(CG_ERR_ARG, "momentum_update: bad arguments (momentum=%g)", momentum);
+  if (reg_begin < 0 || reg_n < 0 || reg_begin > n || reg_n > n - reg_begin)
+    return fail(CG_ERR_ARG, "momentum_update: regularised range [%lld, +%lld) outside [0, %lld)",
+                (long long)reg_begin, (long long)reg_n, (long long)n);
+  if (int rc = cg::all_distinct("momentum_update: param / grad / accum", {param, grad, accum}))
+    return rc;
+  if (n == 0) return ok();
+  CG_HIP(cg::launch_momentum(param, grad, accum, n, lr, momentum, grad_scale, reg, reg_begin, reg_n,
+                             reinterpret_cast<hipStream_t>(stream)));
   return ok();
 }
 

@@ -82,11 +82,15 @@ class _ChebFilter:
     """ONE Chebyshev filter of a device model: its forward and backward C-ABI
     calls and the basis saved between them -- in the planes layout where it
     applies, else rows (``layout`` overrides the choice).  ``W``, ``dW`` and ``out``
-    are the caller's; the plan and the workspace are the ``owner``'s (a FlatTrainer)."""
+    are the caller's; the plan and the workspace are the ``owner``'s (a FlatTrainer),
+    unless ``plan`` (with its vertex count ``M``) names this filter's own graph:
+    a level of the cgcnn pyramid."""
 
-    def __init__(self, owner, fi, fo, K, act, W, dW, out, layout=None):
-        N, M, plan = owner.N, owner.M, owner.plan
-        self.o, self.W, self.dW, self.out = owner, W, dW, out
+    def __init__(self, owner, fi, fo, K, act, W, dW, out, layout=None, plan=None, M=None):
+        N = owner.N
+        plan = owner.plan if plan is None else plan
+        M = owner.M if M is None else int(M)
+        self.o, self.W, self.dW, self.out, self.plan = owner, W, dW, out, plan
         self.dims, self.act = (plan.handle, N, fi, K, fo), ops.ACTS[act]
         if layout is None:
             layout = "planes" if plan.basis_elems(N, fi, K, fo, "planes") else "rows"
@@ -99,7 +103,7 @@ class _ChebFilter:
     wshape = staticmethod(lambda fi, fo, K, M: (fi * K, fo))
 
     def ws_bytes(self):
-        return max(self.o.plan.workspace_bytes(*self.dims[1:]))
+        return max(self.plan.workspace_bytes(*self.dims[1:]))
 
     def forward(self, x, res, s):
         """out = act(filter(x; W) + res)."""

@@ -1036,6 +1036,137 @@ def rmsprop_update(param, grad, ms, mom, lr=1e-3, rho=0.9, momentum=0.0, eps=1e-
               float(rho), float(momentum), float(eps), float(grad_scale), _stream(param))
 
 
+def _check_reg_range(n: int, reg_begin: int, reg_n: int):
+    reg_begin, reg_n = int(reg_begin), int(reg_n)
+    if reg_begin < 0 or reg_n < 0 or reg_begin + reg_n > n:
+        raise ValueError(f"regularised range [{reg_begin}, {reg_begin + reg_n}) outside [0, {n})")
+    return reg_begin, reg_n
+
+
+def momentum_update(param, grad, accum=None, lr=1e-3, momentum=0.9, grad_scale=1.0, reg=0.0,
+                    reg_begin: int = 0, reg_n: int = 0):
+    """In-place tf.train.MomentumOptimizer step (lib/models.py:24-55; TF 1.x
+    ApplyMomentum, no Nesterov) with the L2 term: g = grad * grad_scale, plus
+    reg * param on the elements [reg_begin, reg_begin + reg_n); accum = accum *
+    momentum + g; param -= lr * accum.  ``accum`` starts at zeros; momentum == 0
+    is GradientDescentOptimizer (sgd_update's arithmetic) and takes no accum."""
+    ts = [("param", param), ("grad", grad)] + ([("accum", accum)] if accum is not None else [])
+    for name, t in ts:
+        _check_dev(name, t)
+        if not t.is_contiguous() or t.numel() != param.numel():
+            raise ValueError(f"{name} must be contiguous with param's {param.numel()} elements")
+    if not float(momentum) >= 0.0:
+        raise ValueError(f"momentum must be >= 0, got {momentum}")
+    if momentum != 0 and accum is None:
+        raise ValueError("momentum != 0 needs the accum slot")
+    reg_begin, reg_n = _check_reg_range(param.numel(), reg_begin, reg_n)
+    _lib.call("cg_momentum_update", _p(param), _p(grad), _p(accum), param.numel(), float(lr),
+              float(momentum), float(grad_scale), float(reg), reg_begin, reg_n, _stream(param))
+
+
+# -- the class loss of the cgcnn classifier (lib/models.py:24-55) --------------------
+ClassXent = collections.namedtuple("ClassXent", ("loss", "dlogits", "pred", "correct", "status"))
+
+
+def class_labels(labels, C: int, device) -> torch.Tensor:
+    """Class ids [N] as the int32 device tensor cg_class_xent_ema reads.  Host
+    labels (numpy, lists, CPU tensors) are validated against [0, C) before the
+    upload (ValueError; once per dataset); a device tensor is taken as it is --
+    the kernel clamps what it indexes with, gives such a row NaN and reports it
+    in its status word (``class_xent_call(..., check=True)`` raises)."""
+    if isinstance(labels, torch.Tensor) and labels.is_cuda:
+        if labels.dtype.is_floating_point or labels.dtype == torch.bool:
+            raise TypeError(f"labels must be integers, got {labels.dtype}")
+        return labels.to(dtype=torch.int32).contiguous()
+    a = np.asarray(labels.numpy() if isinstance(labels, torch.Tensor) else labels)
+    if a.dtype.kind not in "iu":
+        raise TypeError(f"labels must be integers, got {a.dtype}")
+    if a.ndim != 1:
+        raise ValueError(f"labels must be [N] class ids, got shape {a.shape}")
+    if a.size and (a.min() < 0 or a.max() >= C):
+        raise ValueError(f"labels must lie in [0, {C}), got [{a.min()}, {a.max()}]")
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(device)
+
+
+def class_xent_workspace_bytes(N: int, C: int, reg_n: int = 0) -> int:
+    return _ws_bytes("cg_class_xent_workspace_bytes", int(N), int(C), int(reg_n))[0]
+
+
+def class_xent_call(logits, labels, params=None, reg_begin: int = 0, reg_n: int = 0,
+                    reg_scale: float = 0.0, need_grad: bool = True, ema=None, decay: float = 0.9,
+                    want_pred: bool = False, check: bool = False, ws=None,
+                    out_dlogits=None) -> ClassXent:
+    """cg_class_xent_ema on logits [N, C] and int32 labels [N] (class_labels):
+    loss [1] = mean softmax cross-entropy + reg_scale * 1/2 sum params[reg_begin :
+    reg_begin + reg_n]^2; with need_grad dlogits = (softmax - onehot) / N; ``ema``
+    (fp32 [3], updated in place) the loss moving average; with want_pred the
+    first-maximum argmax [N] and the device count [1] of correct rows.
+    ``status`` [1] holds the first row + 1 whose label is outside [0, C) (0:
+    none); check=True reads it (one sync) and raises ValueError."""
+    _check_dev("logits", logits)
+    _check_dev("labels", labels, torch.int32)
+    if logits.dim() != 2:
+        raise ValueError("logits must be [N, C]")
+    N, C = (int(d) for d in logits.shape)
+    if tuple(labels.shape) != (N,):
+        raise ValueError(f"labels must be [{N}], got {tuple(labels.shape)}")
+    logits, labels = logits.contiguous(), labels.contiguous()
+    reg_begin, reg_n = int(reg_begin), int(reg_n)
+    if reg_n:
+        if params is None:
+            raise ValueError("a regularised range needs params")
+        _check_dev("params", params)
+        if not params.is_contiguous():
+            raise ValueError("params must be contiguous")
+        _check_reg_range(params.numel(), reg_begin, reg_n)
+    _check_opt("ema", ema, 3, False)
+    dev = logits.device
+    if ws is None:
+        ws, _ = _workspace("cg_class_xent_workspace_bytes", N, C, reg_n, device=dev)
+    loss = torch.empty((1,), device=dev, dtype=torch.float32)
+    dlogits = _out("out_dlogits", out_dlogits, (N, C), dev) if need_grad else None
+    i32 = dict(device=dev, dtype=torch.int32)
+    pred = torch.empty((N,), **i32) if want_pred else None
+    correct = torch.empty((1,), **i32) if want_pred else None
+    status = torch.empty((1,), **i32)
+    _lib.call("cg_class_xent_ema", _p(logits), _p(labels), N, C, _p(params) if reg_n else None,
+              reg_begin, reg_n, float(reg_scale), _p(loss), _p(dlogits), _p(ema), float(decay),
+              _p(pred), _p(correct), _p(status), _p(ws), ws.numel(), _stream(logits))
+    if check:
+        bad = int(status.item())
+        if bad:
+            raise ValueError(f"label of row {bad - 1} lies outside [0, {C})")
+    return ClassXent(loss, dlogits, pred, correct, status)
+
+
+class _ClassXent(torch.autograd.Function):
+    """The loss; dlogits comes out of the same launch and is handed out, times
+    the incoming scalar, in the backward (as _SeqXentHead does).  The L2 term's
+    gradient is the optimizer's (momentum_update's ``reg``), not autograd's."""
+
+    @staticmethod
+    def forward(ctx, logits, labels):
+        need = ctx.needs_input_grad[0]
+        r = class_xent_call(logits, labels, need_grad=need)
+        if need:
+            ctx.save_for_backward(r.dlogits)
+        return r.loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        (dlogits,) = ctx.saved_tensors
+        return dlogits * dloss, None
+
+
+def class_xent(logits, labels):
+    """mean_n sparse_softmax_cross_entropy_with_logits(logits [N, C], labels [N])
+    (lib/graph_model.py:251-253 as commented out) as a loss [1] with its
+    gradient.  labels: host integers (validated against [0, C)) or an integer
+    device tensor.  With gradients disabled the launch is the evaluation form."""
+    _check_dev("logits", logits)
+    return _ClassXent.apply(logits, class_labels(labels, int(logits.shape[-1]), logits.device))
+
+
 # -- bias + activation (lib/graph_conv.py:178-199, fc :220-226) --------------------
 BIAS_ACTS = {"none": _lib.CG_ACT_NONE, "relu": _lib.CG_ACT_RELU, "tanh": _lib.CG_ACT_TANH}
 

@@ -266,9 +266,14 @@ class FlatTrainer:
             self.comm.allreduce_sum_(self.grad, s)
         self._after_exchange(s)
         self.step_count += 1
+        self._optimizer_launch(self.learning_rate(self.step_count - 1), self._grad_scale(world), s)
+
+    def _optimizer_launch(self, lr: float, scale: float, s):
+        """The ONE update launch over ``flat`` (a hook: ``CGCNNModel`` runs Momentum
+        with its L2 term here)."""
         f = ctypes.c_float
         flat, grad, n = self.flat.data_ptr(), self.grad.data_ptr(), self.flat.numel()
-        lr, scale = f(self.learning_rate(self.step_count - 1)), f(self._grad_scale(world))
+        lr, scale = f(lr), f(scale)
         if self.optimizer == "adam":
             st = self._update(flat, grad, self.s1.data_ptr(), self.s2.data_ptr(), n, lr, f(0.9),
                               f(0.999), f(1e-8), self.step_count, scale, s)
@@ -304,6 +309,27 @@ class FlatTrainer:
         return _ev.evaluate(lambda d, l: FlatTrainer.predict(self, d, l, **forward_kw), data, labels)
 
     # -- training loop --------------------------------------------------------------
+    # two hooks of ``fit``; the defaults are the regression models' (labels [S, M, Fout])
+    def _fit_set(self, name, d, l):
+        """One of fit's two (data, labels) pairs on the device, validated.  The
+        labels are rows of 4-byte words that cg_batch_gather copies unchanged and
+        that ``evaluate`` accepts."""
+        _, M, Fout = (int(v) for v in self.dout.shape)
+        f32 = dict(device=self.device, dtype=torch.float32)
+        d = torch.as_tensor(d).to(**f32).contiguous()
+        l = torch.as_tensor(l).to(**f32).contiguous()
+        if d.dim() != 3 or int(d.shape[1]) != M:
+            raise ValueError(f"fit: {name}_data must be [samples, M = {M}, channels], got {tuple(d.shape)}")
+        if int(l.shape[0]) != int(d.shape[0]):
+            raise ValueError(f"fit: {name} data and labels differ in their number of samples")
+        if l.numel() != int(d.shape[0]) * M * Fout:
+            raise ValueError(f"fit: {name}_labels must hold [samples, {M}, {Fout}] values")
+        return d, l
+
+    def _fit_label_batch(self):
+        """The buffer a step's labels are gathered into, as ``train_step`` takes them."""
+        return torch.empty(tuple(self.dout.shape), device=self.device, dtype=torch.float32)
+
     def fit(self, train_data, train_labels, val_data, val_labels, num_epochs=20, eval_frequency=200,
             rng=None, verbose=True, stream=None, rank=None):
         """GraphModel.fit (lib/graph_model.py:124-197): ``int(num_epochs * S / B)``
@@ -329,7 +355,7 @@ class FlatTrainer:
         ``verbose`` prints the reference's progress lines (:169-175, :192); the
         learning rate shown is the one the last step applied.  Checkpoints are
         not written."""
-        N, M, Fout = (int(v) for v in self.dout.shape)
+        N = int(self.dout.shape[0])
         world = self.world
         if world > 1 and rng is None:
             raise ValueError("fit: rng=None draws from this process's global numpy state; with "
@@ -342,28 +368,19 @@ class FlatTrainer:
         if not 0 <= int(rank) < world:
             raise ValueError(f"fit: rank {rank} outside [0, {world})")
         f32 = dict(device=self.device, dtype=torch.float32)
-        sets = []
-        for name, d, l in (("train", train_data, train_labels), ("val", val_data, val_labels)):
-            d = torch.as_tensor(d).to(**f32).contiguous()
-            l = torch.as_tensor(l).to(**f32).contiguous()
-            if d.dim() != 3 or int(d.shape[1]) != M:
-                raise ValueError(f"fit: {name}_data must be [samples, M = {M}, channels], got {tuple(d.shape)}")
-            if int(l.shape[0]) != int(d.shape[0]):
-                raise ValueError(f"fit: {name} data and labels differ in their number of samples")
-            if l.numel() != int(d.shape[0]) * M * Fout:
-                raise ValueError(f"fit: {name}_labels must hold [samples, {M}, {Fout}] values")
-            sets.append((d, l))
-        (data, labels), (val_data, val_labels) = sets
+        (data, labels), (val_data, val_labels) = (
+            self._fit_set(name, d, l)
+            for name, d, l in (("train", train_data, train_labels), ("val", val_data, val_labels)))
         S, B = int(data.shape[0]), N * world
         num_steps = int(num_epochs * S / B)
         sched = fit_schedule(S, B, num_steps, rng)  # refuses S < B
         if num_steps < 1:
             raise ValueError(f"fit: num_epochs = {num_epochs} over {S} samples is less than one batch of {B}")
-        labels = labels.view(S, M * Fout)
-        row, lrow = data.numel() // S, M * Fout
+        row, lrow = data.numel() // S, labels.numel() // S
+        labels = labels.view(S, lrow)
         idx = torch.from_numpy(sched).to(self.device)
         x_b = torch.empty((N,) + tuple(data.shape[1:]), **f32)
-        y_b = torch.empty((N, M, Fout), **f32)
+        y_b = self._fit_label_batch()
         s = self._stream(stream)
         gather = _lib.lib().cg_batch_gather
         dp, lp, xp, yp = data.data_ptr(), labels.data_ptr(), x_b.data_ptr(), y_b.data_ptr()

@@ -647,6 +647,36 @@ int cg_seq_xent_head(const float* hs, const float* w, const float* b, const int3
                      float* db, void* ws, size_t ws_bytes, void* hip_stream);
 
 /* ---------------------------------------------------------------------------
+ * The class loss of the pooled cgcnn classifier (lib/models.py:24-55; the
+ * statements the fork left in comments at lib/graph_model.py:249-258, :265-273;
+ * cgcnn.CGCNNModel).  Additive to version 301.  logits [N][C], labels [N]:
+ *   ce[n]   = max_n + log sum_c exp(logits[n][c] - max_n) - logits[n][labels[n]]
+ *   loss[0] = (1/N) sum_n ce[n]
+ *             + reg_scale * 1/2 sum_{i in [reg_begin, reg_begin + reg_n)} params[i]^2
+ *   dlogits = (exp(logits - lse) - [c == label]) / N          NULL: evaluation
+ *   ema     = {biased, average, local_step} of ExponentialMovingAverage(decay)
+ *             of loss[0], cg_mse_loss_ema's zero-debias convention (NULL: skip)
+ *   pred[n] = the FIRST maximum of row n (NULL: skip); correct[0] = the number
+ *             of rows with pred[n] == labels[n] (NULL: skip)
+ * One wave per row, lane-strided over the classes: any C >= 1.  Every sum runs
+ * in a fixed order (per-row and per-chunk partials in the workspace, then one
+ * small reduction launch; no atomics): repeated calls agree bitwise.  A label
+ * outside [0, C) is not used as an index: that row reads a clamped column, its
+ * ce and dlogits (and so the loss) are NaN, and status[0] (NULL: skip) receives
+ * the first such row + 1, 0 when every label is in range.  params may be NULL
+ * with reg_n == 0; the caller vouches that the range lies inside its buffer.
+ * Null logits / labels / loss, N or C < 1, N*C >= 2^31, a negative range,
+ * decay outside [0, 1] with ema, dlogits == logits and a workspace smaller than
+ * cg_class_xent_workspace_bytes return CG_ERR_ARG before any device work.
+ * ------------------------------------------------------------------------- */
+int cg_class_xent_workspace_bytes(int32_t N, int32_t C, int64_t reg_n, size_t* bytes);
+int cg_class_xent_ema(const float* logits, const int32_t* labels, int32_t N, int32_t C,
+                      const float* params, int64_t reg_begin, int64_t reg_n, float reg_scale,
+                      float* loss, float* dlogits, float* ema, float decay, int32_t* pred,
+                      int32_t* correct, int32_t* status, void* workspace, size_t ws_bytes,
+                      void* stream);
+
+/* ---------------------------------------------------------------------------
  * The two seams of the closeness / period / trend gconv-LSTM networks
  * (lib/gconv_lstm.py:431-607; glstm_period.GLSTMPeriodModel).  Additive to
  * version 301.  B branches, 1 <= B <= 4; y, w, dy, dw, h, dh, H and seed are
@@ -753,6 +783,19 @@ int cg_sgd_update(float* param, const float* grad, int64_t n, float lr, float gr
                   void* stream);
 int cg_rmsprop_update(float* param, const float* grad, float* ms, float* mom, int64_t n, float lr,
                       float rho, float momentum, float eps, float grad_scale, void* stream);
+/* The cgcnn classifier's update (lib/models.py:24-55: tf.train.MomentumOptimizer,
+ * GradientDescentOptimizer when momentum == 0; TF 1.x ApplyMomentum, no
+ * Nesterov) with the L2 term of the regularised variables.  On n fp32 parameters:
+ *   g = grad * grad_scale, + reg * param for i in [reg_begin, reg_begin + reg_n)
+ *   momentum != 0: accum = accum * momentum + g; param -= lr * accum  (accum starts at zeros)
+ *   momentum == 0: param -= g * lr     (cg_sgd_update's arithmetic; accum unused, may be NULL)
+ * One launch; float4 lanes with a scalar tail when the three pointers are
+ * 16-byte aligned, scalar lanes otherwise; the range needs no alignment.
+ * CG_ERR_ARG: null param / grad, accum NULL with momentum != 0, n < 0, momentum
+ * negative or NaN, a range outside [0, n), two of the buffers being one. */
+int cg_momentum_update(float* param, const float* grad, float* accum, int64_t n, float lr,
+                       float momentum, float grad_scale, float reg, int64_t reg_begin,
+                       int64_t reg_n, void* stream);
 
 /* cg_cheb_backward followed by cg_adam_update(W, dW, m, v, ...) with the
  * optimizer step applied by the dW reduction itself -- for a training step

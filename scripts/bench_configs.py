@@ -26,6 +26,11 @@
       layers, out 2) against the same network composed from ops.cheb_conv + add +
       ops.bias_act under autograd, interleaved
 
+  CG  the training step of the pooled cgcnn classifier (cgcnn.CGCNNModel) at usage.ipynb's
+      network (F [32, 64], K [20, 20], p [4, 2], M [512, 10], batch 100) on the MNIST pyramid
+      of golden_B, against GraphConv.cgcnn_inference under torch autograd with
+      torch.nn.functional.cross_entropy and torch.optim.SGD(momentum, weight_decay), interleaved
+
   FIT the training loop around a step: ResGNN at config R's shape and GLSTMModel at config
       E's model step, 2 048 synthetic samples on the device -- (a) train_step on one static
       batch (the floor), (b) the loop a user writes without fit, train_step(data[i],
@@ -38,7 +43,7 @@ rounds; alg_GBps uses SURVEY.md §8d's algorithmic bytes.  Each line carries a
 `cpu_baseline`: the oracle's fwd+bwd of the same config on the host cores
 (bench.py's CPU legs -- the only place outside tests/ that runs oracle/),
 median of the timed passes, with the sub-batch and pass count stated.
-Usage: python scripts/bench_configs.py [A C1 C2 D E EF EP FIT GC R RF S] [--d-batch N] [--layout auto|rows|planes]
+Usage: python scripts/bench_configs.py [A C1 C2 CG D E EF EP FIT GC R RF S] [--d-batch N] [--layout auto|rows|planes]
                                        [--no-cpu] [--cpu-seconds S]
 """
 from __future__ import annotations
@@ -563,6 +568,63 @@ def gconv_net_config(dev, N=100, T=(3, 3, 3), H=64, K=2, nres=4, out_f=2, runs=5
             "out": out_f, "steps": res}
 
 
+def cgcnn_config(dev, N=100, F=(32, 64), K=(20, 20), p=(4, 2), Mfc=(512, 10), reg=5e-4, keep=0.5,
+                 runs=5):
+    """CG: one CGCNNModel training step of usage.ipynb's network (F [32, 64], K
+    [20, 20], p [4, 2], M [512, 10], batch 100, mpool1, b1relu, regularization
+    5e-4, dropout 0.5, momentum 0.9) on the MNIST pyramid of golden_B, against
+    the same network as GraphConv.cgcnn_inference under torch autograd with
+    torch.nn.functional.cross_entropy and torch.optim.SGD(momentum 0.9,
+    weight_decay on the fc / logits variables) -- the composition has no
+    dropout (cgcnn_inference applies none), so it does less.  HIP events, the
+    two interleaved run by run; per-run numbers, medians and ranges."""
+    from cnn_graph_amd import CGCNNModel, coarsening, graph
+    from cnn_graph_amd.graph_conv import GraphConv
+    with np.load(os.path.join(ROOT, "tests", "golden", "golden_B.npz"), allow_pickle=False) as z:
+        g = {k: z[k] for k in z.files}
+    A = scipy.sparse.csr_matrix((g["A_data"], g["A_indices"], g["A_indptr"]), shape=tuple(g["A_shape"]))
+    graphs, perm = coarsening.coarsen(A, 4, rids=[g[f"rid{i}"] for i in range(4)], verbose=False)
+    L = [graph.laplacian(G, normalized=True) for G in graphs]
+    rng = np.random.default_rng(3)
+    x = torch.from_numpy(coarsening.perm_data(rng.random((N, A.shape[0])), perm).astype(np.float32)).to(dev)
+    labels_h = rng.integers(0, Mfc[-1], N)
+    labels = ops.class_labels(labels_h, Mfc[-1], dev)
+    labels64 = labels.long()
+    model = CGCNNModel(L, N, list(F), list(K), list(p), list(Mfc), regularization=reg, dropout=keep,
+                       learning_rate=0.02, decay_rate=0.95, decay_steps=550, momentum=0.9, device=dev)
+    gc = GraphConv(filter="chebyshev5", brelu="b1relu", pool="mpool1", device=dev)
+    gc.cgcnn_inference(x, L, F, K, p, Mfc)  # creates the variables
+    conv = [w for n, w in gc.weights.items() if n.startswith("conv")]
+    dense = [w for n, w in gc.weights.items() if not n.startswith("conv")]
+    opt = torch.optim.SGD([{"params": conv, "weight_decay": 0.0}, {"params": dense, "weight_decay": reg}],
+                          lr=0.02, momentum=0.9)
+
+    def autograd_step():
+        opt.zero_grad(set_to_none=True)
+        loss = torch.nn.functional.cross_entropy(gc.cgcnn_inference(x, L, F, K, p, Mfc), labels64)
+        loss.backward()
+        opt.step()
+
+    def device_step():
+        model.train_step(x, labels)
+
+    for _ in range(3):
+        device_step(), autograd_step()
+    torch.cuda.synchronize()
+    r = {"device": [], "autograd": []}
+    for _ in range(runs):
+        r["device"].append(round(ev_ms(device_step, 5), 4))
+        r["autograd"].append(round(ev_ms(autograd_step, 5), 4))
+    med = {k: round(float(np.median(v)), 4) for k, v in r.items()}
+    return {"config": "CG", "M": [int(l.shape[0]) for l in L], "N": N, "F": list(F), "K": list(K),
+            "p": list(p), "M_fc": list(Mfc), "params": int(model.flat.numel()),
+            "runs_ms": r, "median_ms": med,
+            "device_range_ms": [min(r["device"]), max(r["device"])],
+            "autograd_range_ms": [min(r["autograd"]), max(r["autograd"])],
+            "device_below_autograd_range": bool(med["device"] < min(r["autograd"])),
+            "samples_per_s": round(N / (med["device"] * 1e-3), 1)}
+
+
 def seq_head_config(dev, T=12, N=128, Fin=2, H=32, K=3, keep=0.8, runs=5):
     """S: the gconvRNN sequence model (gconv_rnn.GConvRNNModel) at config E's
     graph and shape.  (a) the fused head (cg_seq_xent_head: mask, logits,
@@ -789,6 +851,8 @@ def main():
             out = fit_config(dev)
         elif name == "GC":
             out = gconv_net_config(dev)
+        elif name == "CG":
+            out = cgcnn_config(dev)
         elif name == "R":
             out = resgnn_config(dev)
             cpu = lambda: bench.cpu_baseline_resgnn(graph_e()[1], 2, 100, 2, 32, 20, 4,  # noqa: E731
