@@ -17,11 +17,12 @@ Modules
   glstm_period  GLSTMPeriodModel: the closeness / period / trend gconv-LSTM networks
   gconv_net   GConvNetModel: the pure graph-convolution networks (inference_gconv*)
   cgcnn       CGCNNModel: the pooled cgcnn classifier (lib/models.py), trained on device
+  dense_rnn   LSTMRNNModel: the dense LSTM baseline of gconvRNN.Model (model_type='lstm')
 """
 __version__ = "0.1.0"
 
 __all__ = ["graph", "plan", "ops", "graph_conv", "filter", "coarsening", "dist", "GLSTMPeriodModel",
-           "GConvNetModel", "CGCNNModel"]
+           "GConvNetModel", "CGCNNModel", "LSTMRNNModel"]
 
 
 def __getattr__(name):
@@ -35,4 +36,7 @@ def __getattr__(name):
     if name == "CGCNNModel":
         from .cgcnn import CGCNNModel
         return CGCNNModel
+    if name == "LSTMRNNModel":
+        from .dense_rnn import LSTMRNNModel
+        return LSTMRNNModel
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -153,6 +153,16 @@ _SIGNATURES = {
     "cg_class_xent_workspace_bytes": ([_c_i32, _c_i32, _c_i64, ctypes.POINTER(_c_sz)], _c_int),
     "cg_class_xent_ema": ([_vp, _vp, _c_i32, _c_i32, _vp, _c_i64, _c_i64, ctypes.c_float, _vp, _vp,
                            _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _c_sz, _vp], _c_int),
+    "cg_class_xent_sum": ([_vp, _vp, _c_i32, _c_i32, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp,
+                           _vp, _c_sz, _vp], _c_int),
+    # the dense LSTM baseline: all steps in one launch per direction
+    "cg_dlstm_supported": ([_c_i32, ctypes.POINTER(_c_i32)], _c_int),
+    "cg_dlstm_workspace_bytes": ([_c_i32, _c_i32, _c_i32, ctypes.POINTER(_c_sz),
+                                  ctypes.POINTER(_c_sz)], _c_int),
+    "cg_dlstm_seq_forward": ([_c_i32, _c_i32, _c_i32, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp,
+                              _vp, _c_sz, _vp], _c_int),
+    "cg_dlstm_seq_backward": ([_c_i32, _c_i32, _c_i32, _vp, _vp, _vp, _vp, ctypes.c_float, _vp, _vp,
+                               _c_sz, _vp], _c_int),
     # the branch seams: host arrays of B device pointers / sizes / seeds
     "cg_branch_merge_forward": ([_c_i32, _c_i32, _c_i32, _c_i32, _pp, _pp, _vp, _vp], _c_int),
     "cg_branch_merge_backward": ([_c_i32, _c_i32, _c_i32, _c_i32, _vp, _pp, _pp, _pp, _pp, _c_i32,

@@ -474,11 +474,27 @@ hipError_t launch_seq_xent(const float* hs, const float* w, const float* b, cons
 // logits [N][C], labels [N]; reg: the first of reg_n regularised parameters
 // (reg_n == 0: none); ws: class_xent_ws_bytes.  dlogits, ema, pred, correct and
 // status are nullable.
+// row_scale multiplies the rows' ce sum and (softmax - onehot): 1/N rounded
+// from double for the mean (cg_class_xent_ema), the caller's loss_scale for
+// cg_class_xent_sum.
 size_t class_xent_ws_bytes(int N, int64_t reg_n);
 hipError_t launch_class_xent(const float* logits, const int32_t* labels, int N, int C,
-                             const float* reg, int64_t reg_n, float reg_scale, float* loss,
-                             float* dlogits, float* ema, float decay, int32_t* pred,
+                             const float* reg, int64_t reg_n, float reg_scale, float row_scale,
+                             float* loss, float* dlogits, float* ema, float decay, int32_t* pred,
                              int32_t* correct, int32_t* status, float* ws, hipStream_t s);
+
+// ---- dense LSTM baseline, all steps in one launch per direction (dense_lstm.hip) ----
+// gx [T][N][4H] (gate blocks i | j | f | o), Wh [H][4H], hs / cs [T][N][H], act
+// and dpre [T][N][4H] in gx's layout.  dlstm_ok: H % 16 == 0, 16 <= H <= 128;
+// dlstm_resident: Wh staged in LDS (both kernels' images fit in kLdsBytes).
+bool dlstm_ok(int H);
+bool dlstm_resident(int H);
+size_t dlstm_lds_bytes(int H, bool backward, bool resident);
+hipError_t launch_dlstm_fwd(int T, int N, int H, const float* gx, const float* Wh,
+                            const float* bias, float forget_bias, float* hs, float* cs, float* act,
+                            hipStream_t s);
+hipError_t launch_dlstm_bwd(int T, int N, int H, const float* dhs, const float* act,
+                            const float* cs, const float* Wh, float* dpre, hipStream_t s);
 
 // ---- gconv-LSTM cell (lstm.hip) ------------------------------------------------
 // gates: 0 = reference gate functions (tan / sigmoid / sigmoid / tanh,

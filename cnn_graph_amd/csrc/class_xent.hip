@@ -21,6 +21,10 @@
 // A label outside [0, C) is never used as an index: the row reads x[n][clamped],
 // its ce and dlogits are NaN (TF's GPU kernel does the same), and status[0]
 // receives the first such row + 1 (0: none).
+//
+// cg_class_xent_sum (the dense LSTM baseline's loss, lib/gconvRNN.py:328-332) is
+// the same two launches with the caller's loss_scale in the place of 1/N (the
+// kernels' inv_n), no regularised range and no moving average.
 #include "cg_internal.h"
 
 #include <cmath>
@@ -159,15 +163,15 @@ size_t class_xent_ws_bytes(int N, int64_t reg_n) {
 }
 
 hipError_t launch_class_xent(const float* logits, const int32_t* labels, int N, int C,
-                             const float* reg, int64_t reg_n, float reg_scale, float* loss,
-                             float* dlogits, float* ema, float decay, int32_t* pred,
+                             const float* reg, int64_t reg_n, float reg_scale, float row_scale,
+                             float* loss, float* dlogits, float* ema, float decay, int32_t* pred,
                              int32_t* correct, int32_t* status, float* ws, hipStream_t s) {
   const int chunks = reg_n > 0 ? mse_chunks(reg_n) : 0;
   ClassXentArgs a;
   a.x = logits, a.labels = labels, a.N = N, a.C = C;
   a.reg = reg, a.reg_n = reg_n, a.reg_chunk = chunks ? (reg_n + chunks - 1) / chunks : 0;
   a.row_blocks = (N + 3) / 4;
-  a.inv_n = float(1.0 / double(N));
+  a.inv_n = row_scale;
   a.dx = dlogits, a.pred = pred;
   a.ce = ws, a.flag = reinterpret_cast<int32_t*>(ws + N), a.slab = ws + 2 * size_t(N);
   hipLaunchKernelGGL(k_class_xent, dim3(unsigned(a.row_blocks + chunks)), dim3(256), 0, s, a);

@@ -119,9 +119,28 @@ int cg_class_xent_ema(const float* logits, const int32_t* labels, int32_t N, int
   if (int rc = need_ws("class_xent_ema", workspace, ws_bytes, al256(cg::class_xent_ws_bytes(N, reg_n))))
     return rc;
   CG_HIP(cg::launch_class_xent(logits, labels, N, C, reg_n > 0 ? params + reg_begin : nullptr, reg_n,
-                               reg_scale, loss, dlogits, ema, decay, pred, correct, status,
-                               static_cast<float*>(workspace),
+                               reg_scale, float(1.0 / double(N)), loss, dlogits, ema, decay, pred,
+                               correct, status, static_cast<float*>(workspace),
                                reinterpret_cast<hipStream_t>(stream)));
+  return ok();
+}
+
+int cg_class_xent_sum(const float* logits, const int32_t* labels, int32_t N, int32_t C,
+                      float loss_scale, float* loss, float* dlogits, float* ce, int32_t* pred,
+                      int32_t* correct, int32_t* status, void* workspace, size_t ws_bytes,
+                      void* stream) {
+  if (!logits || !labels || !loss) return fail(CG_ERR_ARG, "class_xent_sum: null pointer");
+  if (N < 1 || C < 1) return fail(CG_ERR_ARG, "class_xent_sum: bad sizes (N=%d C=%d)", N, C);
+  if (int rc = cg::below_2_31("class_xent_sum: logits", N, C)) return rc;
+  if (int rc = cg::no_alias("class_xent_sum: dlogits", {dlogits}, {logits})) return rc;
+  if (int rc = need_ws("class_xent_sum", workspace, ws_bytes, al256(cg::class_xent_ws_bytes(N, 0))))
+    return rc;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  float* ws = static_cast<float*>(workspace);
+  CG_HIP(cg::launch_class_xent(logits, labels, N, C, nullptr, 0, 0.f, loss_scale, loss, dlogits,
+                               nullptr, 0.f, pred, correct, status, ws, s));
+  if (ce)  // the rows' ce are the workspace's first N floats
+    CG_HIP(hipMemcpyAsync(ce, ws, size_t(N) * sizeof(float), hipMemcpyDeviceToDevice, s));
   return ok();
 }
 

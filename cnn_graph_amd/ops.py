@@ -1742,3 +1742,181 @@ def concat_drop(hs, keep: float = 1.0, seeds=None):
     for bit, without the dropped tensors and the concat copy.  seed_b is the
     folded seed (``seed + DROP_WEYL * offset``); keep == 1 is a plain concat."""
     return _ConcatDrop.apply(float(keep), None if seeds is None else tuple(int(s) for s in seeds), *hs)
+
+
+# -- the dense LSTM baseline (lib/gconvRNN.py:280-285, :300; TF 1.x BasicLSTMCell) ----
+DENSE_LSTM_PATHS = ("seq", "steps")
+
+
+def dense_lstm_supported(H: int) -> bool:
+    """Whether the one-launch kernels (cg_dlstm_seq_*) serve this hidden size."""
+    return _supported("cg_dlstm_supported", int(H))
+
+
+def _dlstm_ws(T: int, N: int, H: int, dev, pick: int):
+    nb = _ws_bytes("cg_dlstm_workspace_bytes", T, N, H, sizes=2)[pick]
+    return (torch.empty(nb, device=dev, dtype=torch.uint8) if nb else None), nb
+
+
+def dense_lstm_seq_forward(gx, Wh, bias, forget_bias: float = 1.0, need_act: bool = True):
+    """cg_dlstm_seq_forward: gx [T, N, 4H] (gate blocks i | j | f | o), Wh [H, 4H],
+    bias [4H] -> (hs [T, N, H], cs [T, N, H], act [T, N, 4H] or None)."""
+    for name, t in (("gx", gx), ("Wh", Wh), ("bias", bias)):
+        _check_dev(name, t)
+    T, N, G = (int(v) for v in gx.shape)
+    H = G // 4
+    _check_weight("Wh", Wh, H, G)
+    _check_opt("bias", bias, G, aligned=False)
+    if not gx.is_contiguous():
+        raise ValueError("gx must be contiguous")
+    f32 = dict(device=gx.device, dtype=torch.float32)
+    hs, cs = torch.empty((T, N, H), **f32), torch.empty((T, N, H), **f32)
+    act = torch.empty((T, N, G), **f32) if need_act else None
+    ws, nb = _dlstm_ws(T, N, H, gx.device, 0)
+    _lib.call("cg_dlstm_seq_forward", T, N, H, _p(gx), _p(Wh), _p(bias), float(forget_bias), _p(hs),
+              _p(cs), _p(act), _p(ws), nb, _stream(gx))
+    return hs, cs, act
+
+
+def dense_lstm_seq_backward(dhs, act, cs, Wh, forget_bias: float = 1.0):
+    """cg_dlstm_seq_backward: dpre [T, N, 4H] of the whole sequence from the
+    output gradients dhs [T, N, H] and the forward's act and cs."""
+    for name, t in (("dhs", dhs), ("act", act), ("cs", cs), ("Wh", Wh)):
+        _check_dev(name, t)
+    T, N, H = (int(v) for v in cs.shape)
+    _check_weight("Wh", Wh, H, 4 * H)
+    dhs = dhs.contiguous()
+    if dhs.numel() != cs.numel() or act.numel() != 4 * cs.numel() or not act.is_contiguous():
+        raise ValueError("dense_lstm_seq_backward: dhs / act do not match cs")
+    dpre = torch.empty((T, N, 4 * H), device=cs.device, dtype=torch.float32)
+    ws, nb = _dlstm_ws(T, N, H, cs.device, 1)
+    _lib.call("cg_dlstm_seq_backward", T, N, H, _p(dhs), _p(act), _p(cs), _p(Wh), float(forget_bias),
+              _p(dpre), _p(ws), nb, _stream(cs))
+    return dpre
+
+
+def _dlstm_perm(H: int, dev):
+    """Column gather that takes TF's i | j | f | o to the cell kernels' z | i | f | o
+    (z = j), and its inverse."""
+    u = torch.arange(H, device=dev)
+    perm = torch.cat([H + u, u, 2 * H + u, 3 * H + u])
+    return perm, torch.argsort(perm)
+
+
+class _DenseLSTMSeq(torch.autograd.Function):
+    """BasicLSTMCell under static_rnn from the zero state over xs [T*N, C]:
+    ``kernel`` [C + H, 4H] is TF's single variable (Wx its first C rows, Wh the
+    rest), ``bias`` [4H].  path "seq": one cg_gemm_f32 for gx, then ONE launch a
+    direction (cg_dlstm_seq_forward / _backward).  path "steps": the same
+    network from the existing entries, per step cg_gemm_f32 (h Wh) and
+    cg_lstm_cell_forward / _backward with the standard gates on columns
+    permuted to z | i | f | o and forget_bias folded into the f bias.  Either
+    way dWx = xs^T dpre, dWh = hs[0:T-1]^T dpre[1:T] (zeros for T = 1, no
+    zero-row GEMM) and db = cg_bias_grad(dpre) land in one [C + H, 4H] gradient."""
+
+    @staticmethod
+    def forward(ctx, xs, kernel, bias, T: int, N: int, forget_bias: float, path: str):
+        for name, t in (("xs", xs), ("kernel", kernel), ("bias", bias)):
+            _check_dev(name, t)
+        xs = xs.contiguous()
+        C, G = int(xs.shape[1]), int(kernel.shape[1])
+        H = G // 4
+        if xs.shape[0] != T * N or tuple(kernel.shape) != (C + H, 4 * H) or not kernel.is_contiguous():
+            raise ValueError(f"dense_lstm_seq: need xs [T*N, C] and a contiguous kernel [C + H, 4H], "
+                             f"got {tuple(xs.shape)} and {tuple(kernel.shape)}")
+        ctx.dims, ctx.fb, ctx.path = (T, N, C, H), float(forget_bias), path
+        if path == "seq":
+            gx = gemm(xs, kernel[:C]).view(T, N, G)
+            hs, cs, act = dense_lstm_seq_forward(gx, kernel[C:], bias, forget_bias)
+            ctx.save_for_backward(xs, kernel, hs, cs, act)
+            return hs
+        perm, _ = _dlstm_perm(H, xs.device)
+        kp = kernel.index_select(1, perm)
+        bp = bias.index_select(0, perm)
+        bp[2 * H:3 * H] += float(forget_bias)
+        gx = gemm(xs, kp[:C]).view(T, N, G)
+        f32 = dict(device=xs.device, dtype=torch.float32)
+        hs, cs, act = torch.empty((T, N, H), **f32), torch.empty((T, N, H), **f32), torch.empty((T, N, G), **f32)
+        gh = torch.empty((N, G), **f32)
+        for t in range(T):
+            if t:
+                gemm(hs[t - 1], kp[C:], out=gh)
+            lstm_cell_forward(gx[t], gh if t else None, bp, cs[t - 1] if t else None, H, "standard",
+                              out_c=cs[t], out_h=hs[t], out_act=act[t])
+        ctx.save_for_backward(xs, kp, hs, cs, act)
+        return hs
+
+    @staticmethod
+    def backward(ctx, dhs):
+        xs, kernel, hs, cs, act = ctx.saved_tensors
+        T, N, C, H = ctx.dims
+        G = 4 * H
+        dhs = dhs.contiguous()
+        f32 = dict(device=xs.device, dtype=torch.float32)
+        Wh = kernel[C:]
+        if ctx.path == "seq":
+            dpre = dense_lstm_seq_backward(dhs, act, cs, Wh, ctx.fb)
+        else:
+            dpre = torch.empty((T, N, G), **f32)
+            dh_rec, dc = None, None
+            for t in range(T - 1, -1, -1):
+                _, dc = lstm_cell_backward(dhs[t], dh_rec, dc, act[t], cs[t - 1] if t else None, cs[t], H,
+                                           "standard", out_dpre=dpre[t], need_dc_prev=t > 0)
+                if t:
+                    dh_rec = gemm(dpre[t], Wh, trans_b=True)
+        d2 = dpre.view(T * N, G)
+        dk = torch.empty((C + H, G), **f32)
+        gemm(xs, d2, trans_a=True, out=dk[:C])
+        if T > 1:
+            gemm(hs.view(T * N, H)[:(T - 1) * N], d2[N:], trans_a=True, out=dk[C:])
+        else:
+            dk[C:].zero_()
+        db = bias_grad(d2)
+        if ctx.path != "seq":
+            _, inv = _dlstm_perm(H, xs.device)
+            dk, db = dk.index_select(1, inv), db.index_select(0, inv)
+        dx = gemm(d2, kernel[:C], trans_b=True) if ctx.needs_input_grad[0] else None
+        return dx, dk, db, None, None, None, None
+
+
+def dense_lstm_seq(xs, kernel, bias, T: int, N: int, forget_bias: float = 1.0, path: str = "seq"):
+    """hs [T, N, H] of the dense LSTM over xs [T*N, C] (step-major rows), with
+    its gradients (``_DenseLSTMSeq``).  ``path``: "seq" (one launch a direction;
+    H % 16 == 0, 16 <= H <= 128) or "steps" (per-step composition of the
+    existing entries, any H)."""
+    if path not in DENSE_LSTM_PATHS:
+        raise ValueError(f"path must be one of {DENSE_LSTM_PATHS}, got {path!r}")
+    return _DenseLSTMSeq.apply(xs, kernel, bias, int(T), int(N), float(forget_bias), path)
+
+
+ClassXentSum = collections.namedtuple("ClassXentSum", ("loss", "dlogits", "ce", "pred", "correct", "status"))
+
+
+def class_xent_sum(logits, labels, loss_scale: float, need_grad: bool = True, want_ce: bool = False,
+                   want_pred: bool = False, ws=None, out_dlogits=None) -> ClassXentSum:
+    """cg_class_xent_sum on logits [R, C] and int32 labels [R] (class_labels):
+    loss [1] = loss_scale * sum_rows ce; with need_grad dlogits = loss_scale *
+    (softmax - onehot).  No L2 term, no moving average.  ``status`` as in
+    class_xent_call."""
+    _check_dev("logits", logits)
+    _check_dev("labels", labels, torch.int32)
+    if logits.dim() != 2:
+        raise ValueError("logits must be [R, C]")
+    R, C = (int(d) for d in logits.shape)
+    if labels.numel() != R:
+        raise ValueError(f"labels must hold {R} class ids, got {tuple(labels.shape)}")
+    logits, labels = logits.contiguous(), labels.contiguous()
+    dev = logits.device
+    if ws is None:
+        ws, _ = _workspace("cg_class_xent_workspace_bytes", R, C, 0, device=dev)
+    loss = torch.empty((1,), device=dev, dtype=torch.float32)
+    dlogits = _out("out_dlogits", out_dlogits, (R, C), dev) if need_grad else None
+    i32 = dict(device=dev, dtype=torch.int32)
+    ce = torch.empty((R,), device=dev, dtype=torch.float32) if want_ce else None
+    pred = torch.empty((R,), **i32) if want_pred else None
+    correct = torch.empty((1,), **i32) if want_pred else None
+    status = torch.empty((1,), **i32)
+    _lib.call("cg_class_xent_sum", _p(logits), _p(labels), R, C, float(loss_scale), _p(loss),
+              _p(dlogits), _p(ce), _p(pred), _p(correct), _p(status), _p(ws), ws.numel(),
+              _stream(logits))
+    return ClassXentSum(loss, dlogits, ce, pred, correct, status)

@@ -675,6 +675,65 @@ int cg_class_xent_ema(const float* logits, const int32_t* labels, int32_t N, int
                       float* loss, float* dlogits, float* ema, float decay, int32_t* pred,
                       int32_t* correct, int32_t* status, void* workspace, size_t ws_bytes,
                       void* stream);
+/* The same rows with the caller's scale and nothing else (the dense LSTM
+ * baseline's loss, lib/gconvRNN.py:328-332: (1/T) sum_t sum_n ce, a SUM over
+ * the rows and not their mean).  Additive to version 301.
+ *   loss[0] = loss_scale * sum_n ce[n]
+ *   dlogits = loss_scale * (exp(logits - lse) - [c == label])   NULL: evaluation
+ * No L2 term, no moving average.  ce ([N], NULL: skip) receives the rows'
+ * cross-entropies; pred, correct and status as above.  The kernels are
+ * cg_class_xent_ema's: with loss_scale = (float)(1.0 / N) and reg_n = 0 there,
+ * loss and dlogits agree bitwise.  Workspace: cg_class_xent_workspace_bytes(N,
+ * C, 0).  Refusals as above (null logits / labels / loss, N or C < 1, N*C >=
+ * 2^31, dlogits == logits, a short workspace): CG_ERR_ARG before any device work. */
+int cg_class_xent_sum(const float* logits, const int32_t* labels, int32_t N, int32_t C,
+                      float loss_scale, float* loss, float* dlogits, float* ce, int32_t* pred,
+                      int32_t* correct, int32_t* status, void* workspace, size_t ws_bytes,
+                      void* stream);
+
+/* ---------------------------------------------------------------------------
+ * The dense LSTM baseline of lib/gconvRNN.py::Model, model_type='lstm'
+ * (:257-262, :280-285, :314-315; dense_rnn.LSTMRNNModel): a TF 1.x
+ * BasicLSTMCell under static_rnn from the zero state (:300).  Additive to
+ * version 301.  H % 16 == 0 and 16 <= H <= 128, else CG_ERR_UNSUPPORTED
+ * (cg_dlstm_supported reports it).  Gate blocks in TF's column order
+ * i | j | f | o, so the rows of a checkpoint's kernel map across unchanged.
+ *
+ * cg_dlstm_seq_forward: ALL T steps in ONE launch.
+ *   gx [T][N][4H]   the input projection of every step (one cg_gemm_f32 over
+ *                   the T*N rows), Wh [H][4H], bias [4H]
+ *   a   = (gx_t + h_{t-1} Wh) + bias               (step 0 runs no h product)
+ *   c_t = c_{t-1} * sigmoid(a_f + forget_bias) + sigmoid(a_i) * tanh(a_j)
+ *   h_t = tanh(c_t) * sigmoid(a_o)
+ *   hs, cs [T][N][H] OUT;  act [T][N][4H] OUT (NULL: inference): the gate
+ *   activations sigmoid(a_i) | tanh(a_j) | sigmoid(a_f + forget_bias) |
+ *   sigmoid(a_o), gate-major in gx's layout -- act[t][n][g*H + u].  hs is the
+ *   same bits with and without act.
+ * cg_dlstm_seq_backward: the whole BPTT in ONE launch, t = T-1 .. 0.
+ *   dhs [T][N][H]   the loss gradient of every output h_t
+ *   dh = dhs_t + dh_rec;  the gate backward from act and cs;  dpre_t [N][4H]
+ *   (gx's layout) stored;  dh_rec = dpre_t Wh^T;  dc carried in registers.
+ *   dpre [T][N][4H] is the only output: dWx = xs^T dpre and dWh =
+ *   hs[0:T-1]^T dpre[1:T] are cg_gemm_f32 calls with trans_a, db cg_bias_grad.
+ *   forget_bias is accepted for symmetry; act already holds the f gate.
+ * A workgroup owns 16 batch rows for the whole sequence (c / dc in registers,
+ * h_t / dpre_t through LDS as the next product's operand, exact-f32 MFMA); Wh
+ * is staged in LDS for H <= 80 and read from global memory above.  No
+ * workgroup waits on another: no cooperative launch, flags or atomics, and
+ * cg_dlstm_workspace_bytes reports 0 for both directions (workspace may then
+ * be NULL).  Every sum runs in a fixed order: repeated calls agree bitwise.
+ * Null required pointers, sizes < 1, gx / hs / cs / act / dhs / dpre not
+ * 16-byte aligned, an output that is an input (dpre == act among them) and a
+ * workspace shorter than reported return CG_ERR_ARG before any device work.
+ * ------------------------------------------------------------------------- */
+int cg_dlstm_supported(int32_t H, int32_t* supported);
+int cg_dlstm_workspace_bytes(int32_t T, int32_t N, int32_t H, size_t* fwd_bytes, size_t* bwd_bytes);
+int cg_dlstm_seq_forward(int32_t T, int32_t N, int32_t H, const float* gx, const float* Wh,
+                         const float* bias, float forget_bias, float* hs, float* cs, float* act,
+                         void* workspace, size_t ws_bytes, void* stream);
+int cg_dlstm_seq_backward(int32_t T, int32_t N, int32_t H, const float* dhs, const float* act,
+                          const float* cs, const float* Wh, float forget_bias, float* dpre,
+                          void* workspace, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
  * The two seams of the closeness / period / trend gconv-LSTM networks

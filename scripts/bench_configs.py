@@ -15,6 +15,10 @@
       K=3, keep 0.8): the fused per-step softmax head against its composition from
       ops.dropout and torch ops, and the training step with each seam
 
+  SL  the dense LSTM baseline (dense_rnn.LSTMRNNModel) at N=512, T=12, C=1024, H=32 and 128:
+      the training step over the two one-launch sequence kernels (path "seq") against the
+      per-step composition from cg_gemm_f32 and cg_lstm_cell_* (path "steps"), interleaved
+
   EP  the closeness / period / trend step (glstm_period.GLSTMPeriodModel) on config E's
       graph: N=50, T=(3, 3, 3), K=2, at H=128 with fourier_conv and H=32 with cheby_conv,
       in both merge modes; and the two seams alone against their composition from
@@ -43,7 +47,7 @@ rounds; alg_GBps uses SURVEY.md §8d's algorithmic bytes.  Each line carries a
 `cpu_baseline`: the oracle's fwd+bwd of the same config on the host cores
 (bench.py's CPU legs -- the only place outside tests/ that runs oracle/),
 median of the timed passes, with the sub-batch and pass count stated.
-Usage: python scripts/bench_configs.py [A C1 C2 CG D E EF EP FIT GC R RF S] [--d-batch N] [--layout auto|rows|planes]
+Usage: python scripts/bench_configs.py [A C1 C2 CG D E EF EP FIT GC R RF S SL] [--d-batch N] [--layout auto|rows|planes]
                                        [--no-cpu] [--cpu-seconds S]
 """
 from __future__ import annotations
@@ -703,6 +707,45 @@ def seq_head_config(dev, T=12, N=128, Fin=2, H=32, K=3, keep=0.8, runs=5):
     return out
 
 
+def dense_lstm_config(dev, N=512, T=12, C=1024, hidden=(32, 128), keep=0.8, runs=5):
+    """SL: the training step of the dense LSTM baseline (dense_rnn.LSTMRNNModel)
+    with the recurrence on the two sequence launches (path "seq") and on the
+    per-step composition of existing entries (path "steps": cg_gemm_f32 for
+    h Wh plus cg_lstm_cell_forward / _backward, standard gates).  HIP events,
+    the two paths interleaved run by run; per-run numbers, medians and ranges
+    per H, and whether "seq" lies below the range of "steps" (the rule
+    ``path="auto"`` is decided on: at BOTH H, by more than the spread)."""
+    from cnn_graph_amd.dense_rnn import LSTMRNNModel
+    g = torch.Generator(device=dev)
+    g.manual_seed(7)
+    x = 0.5 * torch.randn((N, C, T), device=dev, generator=g)
+    labels = torch.from_numpy(np.random.default_rng(7).integers(0, C, (N, T))).to(dev)
+    out = {"config": "SL", "N": N, "T": T, "C": C, "keep_prob": keep, "runs": runs, "H": {}}
+    paths = ("seq", "steps")
+    for H in hidden:
+        models = {p: LSTMRNNModel(N, T, C, num_hidden=H, keep_prob=keep, device=dev, path=p) for p in paths}
+        losses = {}
+        for p, m in models.items():
+            for _ in range(3):
+                losses[p] = m.train_step(x, labels)
+        torch.cuda.synchronize()
+        per_run = {p: [] for p in paths}
+        for _ in range(runs):
+            for p in paths:  # interleaved: drift hits both alike
+                per_run[p].append(round(ev_ms(lambda: models[p].train_step(x, labels), 5), 4))
+        med = {p: round(float(np.median(v)), 4) for p, v in per_run.items()}
+        rng = {p: [min(v), max(v)] for p, v in per_run.items()}
+        out["H"][str(H)] = {
+            "step_runs_ms": per_run, "step_median_ms": med, "step_range_ms": rng,
+            "loss_after_3_steps": {p: float(v) for p, v in losses.items()},
+            "seq_below_steps_range": bool(rng["seq"][1] < rng["steps"][0]),
+            "steps_below_seq_range": bool(rng["steps"][1] < rng["seq"][0]),
+            "samples_per_s": {p: round(N / (v * 1e-3), 1) for p, v in med.items()}}
+        del models
+    out["seq_wins_at_every_H"] = all(v["seq_below_steps_range"] for v in out["H"].values())
+    return out
+
+
 def fit_config(dev, samples=2048, steps=200, runs=5):
     """FIT: what the loop around a training step costs.  Per model, on a
     synthetic dataset of ``samples`` samples that lives on the device and one
@@ -845,6 +888,8 @@ def main():
             out = glstm_gconv_config(dev, filter=args.filter)
         elif name == "S":
             out = seq_head_config(dev)
+        elif name == "SL":
+            out = dense_lstm_config(dev)
         elif name == "EP":
             out = period_config(dev)
         elif name == "FIT":
