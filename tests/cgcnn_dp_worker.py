@@ -1,20 +1,10 @@
-"""Worker of tests/test_gpu_cgcnn_dp.py (not a test module): one rank of the
-data-parallel training step of cgcnn.CGCNNModel, launched by
-``torch.distributed.run --nproc-per-node 2``.  Both ranks share cuda:0 and
-exchange over gloo (dist.TorchComm), as tests/glstm_dp_worker.py does.  Rank r
-trains on its contiguous shard of a fixed global batch; rank 0 writes both
-replicas' parameters after every step.
-
-  python -m torch.distributed.run --nproc-per-node 2 tests/cgcnn_dp_worker.py OUT.npz
-"""
-import os
-import sys
-
+"""Case of tests/test_gpu_cgcnn_dp.py (not a test module): the data-parallel
+training step of cgcnn.CGCNNModel.  Rank r trains on its contiguous shard of a
+fixed global batch; rank 0 writes both replicas' parameters after every step.
+Run through tests/dp_harness.py (case ``cgcnn_dp_worker``)."""
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import dp_harness as DP
 
 STEPS = 2
 N_GLOBAL, M, F, K, P, MFC = 8, [16, 8], [3, 4], [3, 2], [2, 2], [6, 5]
@@ -50,32 +40,11 @@ def run(L, x, labels, dev, comm):
                        learning_rate=0.05, decay_rate=0.95, decay_steps=1, device=dev, seed=2017,
                        comm=comm)
     xs = torch.from_numpy(np.ascontiguousarray(x)).to(dev)
-    params, losses = [], []
-    for _ in range(STEPS):
-        losses.append(float(model.train_step(xs, labels)))
-        params.append(model.flat.cpu().numpy().copy())
-    torch.cuda.synchronize()
-    return np.stack(params), np.array(losses), (model.reg_begin, model.reg_n)
+    return (*DP.train_steps(model, xs, labels, STEPS), (model.reg_begin, model.reg_n))
 
 
-def main():
-    import torch
-    import torch.distributed as dist
-    from cnn_graph_amd import dist as cdist
-    out = sys.argv[1]
-    rank, world, _ = cdist.init(backend="gloo")
-    dev = torch.device("cuda", 0)
-    torch.cuda.set_device(dev)
+def rank_result(rank, world, dev, comm):
     L, x, labels = problem()
-    lo, hi = cdist.shard(N_GLOBAL, rank, world)
-    Pm, losses, _ = run(L, x[lo:hi], labels[lo:hi], dev, cdist.TorchComm())
-    gathered = [torch.zeros(Pm.size, dtype=torch.float32) for _ in range(world)]
-    dist.all_gather(gathered, torch.from_numpy(Pm.reshape(-1)))
-    if rank == 0:
-        np.savez(out, world=world, P=Pm, P_r1=gathered[1].numpy().reshape(Pm.shape), losses=losses)
-    dist.barrier()
-    dist.destroy_process_group()
-
-
-if __name__ == "__main__":
-    main()
+    lo, hi = DP.shard_of(N_GLOBAL, rank, world)
+    Pm, losses, _ = run(L, x[lo:hi], labels[lo:hi], dev, comm)
+    return dict(P=Pm, P_r1=DP.gather_ranks(Pm)[1], losses=losses)

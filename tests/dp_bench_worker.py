@@ -1,22 +1,13 @@
-"""Worker of tests/test_gpu_dp_bench.py (not a test module): one rank of
-bench.py's data-parallel step schedule (cnn_graph_amd/dp_step.py: forward-
-applied Adam with W / m / v double-buffered, the dW all-reduce between
-backward and the next forward, grad_scale = 1/world) on config B's graph,
-launched by ``torch.distributed.run --nproc-per-node 2``.  Both ranks share
-cuda:0 and exchange over gloo (dist.TorchComm; RCCL refuses two ranks on one
-GPU).  Rank r runs its contiguous shard of a fixed global batch; rank 0 writes
-both replicas' weights after every step for the parent to compare.
-
-  python -m torch.distributed.run --nproc-per-node 2 tests/dp_bench_worker.py OUT.npz
-"""
-import os
-import sys
-
+"""Case of tests/test_gpu_dp_bench.py (not a test module): bench.py's
+data-parallel step schedule (cnn_graph_amd/dp_step.py: forward-applied Adam with
+W / m / v double-buffered, the dW all-reduce between backward and the next
+forward, grad_scale = 1/world) on config B's graph.  Rank r runs its contiguous
+shard of a fixed global batch; rank 0 writes both replicas' weights after every
+step for the parent to compare.  Run through tests/dp_harness.py (case
+``dp_bench_worker``)."""
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import dp_harness as DP
 
 STEPS = 3
 N_GLOBAL, K, FOUT = 32, 25, 32
@@ -25,14 +16,12 @@ N_GLOBAL, K, FOUT = 32, 25, 32
 def problem():
     """Config B's graph (the reference MNIST recipe, M = 976), x with fake
     vertices 0, a fixed upstream dy and the initial W, shared by every rank."""
-    import scipy.sparse
     from conftest import load_golden
-    g = load_golden("golden_B.npz")
-    L = scipy.sparse.csr_matrix((g["L_data"], g["L_indices"], g["L_indptr"]), shape=tuple(g["L_shape"]))
+    L = DP.golden_laplacian("golden_B.npz")
     M = L.shape[0]
     rng = np.random.default_rng(2017)
     x = rng.random((N_GLOBAL, M, 1), dtype=np.float32)
-    x[:, g["fake_rows"], :] = 0
+    x[:, load_golden("golden_B.npz")["fake_rows"], :] = 0
     dy = rng.standard_normal((N_GLOBAL, M, FOUT)).astype(np.float32)
     W0 = (rng.standard_normal((K, FOUT)) * 0.1).astype(np.float32)
     return L, x, dy, W0
@@ -62,26 +51,9 @@ def run(x, dy, W0, L, dev, world, allreduce_with, schedule, layout="orders", gra
     return np.stack(out)
 
 
-def main():
-    import torch
-    import torch.distributed as dist
-    from cnn_graph_amd import dist as cdist
-    out = sys.argv[1]
-    rank, world, _ = cdist.init(backend="gloo")
-    dev = torch.device("cuda", 0)
-    torch.cuda.set_device(dev)
+def rank_result(rank, world, dev, comm):
     L, x, dy, W0 = problem()
-    lo, hi = cdist.shard(N_GLOBAL, rank, world)
-    comm = cdist.TorchComm()
+    lo, hi = DP.shard_of(N_GLOBAL, rank, world)
     Ws = run(x[lo:hi], dy[lo:hi], W0, L, dev, world, lambda t, s: comm.allreduce_sum_(t, s),
              "forward")
-    gathered = [torch.zeros(Ws.size, dtype=torch.float32) for _ in range(world)]
-    dist.all_gather(gathered, torch.from_numpy(Ws.reshape(-1)))
-    if rank == 0:
-        np.savez(out, W=Ws, W_r1=gathered[1].numpy().reshape(Ws.shape), world=world)
-    dist.barrier()
-    dist.destroy_process_group()
-
-
-if __name__ == "__main__":
-    main()
+    return dict(W=Ws, W_r1=DP.gather_ranks(Ws)[1])

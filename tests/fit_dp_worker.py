@@ -1,21 +1,11 @@
-"""Worker of tests/test_gpu_fit_dp.py (not a test module): one rank of a
-data-parallel ``ResGNN.fit``, launched by ``torch.distributed.run
---nproc-per-node 2``.  Both ranks share cuda:0 and exchange through a gloo group
-(dist.TorchComm; RCCL refuses two ranks on one GPU).  Every rank builds the
-same seeded schedule of global batches and trains on its own columns of it;
-rank 0 writes what the parent compares with a one-process fit at the global
-batch.
-
-  python -m torch.distributed.run --nproc-per-node 2 tests/fit_dp_worker.py OUT.npz
-"""
-import os
-import sys
-
+"""Case of tests/test_gpu_fit_dp.py (not a test module): a data-parallel
+``ResGNN.fit``.  Every rank builds the same seeded schedule of global batches
+and trains on its own columns of it; rank 0 writes what the parent compares
+with a one-process fit at the global batch.  Run through tests/dp_harness.py
+(case ``fit_dp_worker``)."""
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import dp_harness as DP
 
 N_GLOBAL, FIN, NFILTER, K, NRES = 4, 2, 8, 4, 1
 S, SV, EPOCHS, EVERY, SEED = 10, 6, 2, 2, 33
@@ -23,10 +13,7 @@ S, SV, EPOCHS, EVERY, SEED = 10, 6, 2, 2, 33
 
 def problem():
     """Graph (golden A's Laplacian) and the datasets shared by every rank."""
-    import scipy.sparse
-    from conftest import load_golden
-    g = load_golden("golden_A.npz")
-    L = scipy.sparse.csr_matrix((g["L_data"], g["L_indices"], g["L_indptr"]), shape=tuple(g["L_shape"]))
+    L = DP.golden_laplacian("golden_A.npz")
     M = L.shape[0]
     rng = np.random.default_rng(9)
     sets = tuple(rng.standard_normal(s).astype(np.float32)
@@ -44,24 +31,7 @@ def run(N, L, sets, comm, dev):
     return net.flat.detach().cpu().numpy(), np.array(acc), np.array(losses), net.step_count
 
 
-def main():
-    import torch
-    import torch.distributed as dist
-    from cnn_graph_amd import dist as cdist
-    out = sys.argv[1]
-    rank, world, _ = cdist.init(backend="gloo")
-    dev = torch.device("cuda", 0)
-    torch.cuda.set_device(dev)
+def rank_result(rank, world, dev, comm):
     L, sets = problem()
-    comm = cdist.TorchComm()
     flat, acc, losses, steps = run(N_GLOBAL // world, L, sets, comm, dev)  # rank: the launcher's
-    flats = [torch.zeros(flat.size, dtype=torch.float32) for _ in range(world)]
-    dist.all_gather(flats, torch.from_numpy(flat))
-    if rank == 0:
-        np.savez(out, flat=flat, flat_r1=flats[1].numpy(), acc=acc, losses=losses, steps=steps, world=world)
-    dist.barrier()
-    dist.destroy_process_group()
-
-
-if __name__ == "__main__":
-    main()
+    return dict(flat=flat, flat_r1=DP.gather_ranks(flat)[1], acc=acc, losses=losses, steps=steps)

@@ -1,21 +1,11 @@
-"""Worker of tests/test_gpu_gconv_net_dp.py (not a test module): one rank of the
-data-parallel training step of gconv_net.GConvNetModel for each of its three
-networks, launched by ``torch.distributed.run --nproc-per-node 2``.  Both ranks
-share cuda:0 and exchange over gloo (dist.TorchComm), as tests/glstm_dp_worker.py
-does.  Rank r trains on its contiguous shard of a fixed global batch; rank 0
-writes both replicas' parameters after every step and its first exchanged
-gradient.
-
-  python -m torch.distributed.run --nproc-per-node 2 tests/gconv_net_dp_worker.py OUT.npz
-"""
-import os
-import sys
-
+"""Case of tests/test_gpu_gconv_net_dp.py (not a test module): the data-parallel
+training step of gconv_net.GConvNetModel for each of its three networks.  Rank
+r trains on its contiguous shard of a fixed global batch; rank 0 writes both
+replicas' parameters after every step and its first exchanged gradient.  Run
+through tests/dp_harness.py (case ``gconv_net_dp_worker``)."""
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import dp_harness as DP
 
 STEPS = 3
 N_GLOBAL, M, T, H, K, R, FOUT = 4, 40, (2, 1, 3), 8, 3, 2, 2
@@ -40,40 +30,17 @@ def run(infer_func, L, x, labels, dev, comm):
                           infer_func=infer_func, learning_rate=1e-3, device=dev, seed=2017, comm=comm)
     xs = torch.from_numpy(np.ascontiguousarray(x)).to(dev)
     ys = torch.from_numpy(np.ascontiguousarray(labels)).to(dev)
-    params, g1 = [], None
-    for _ in range(STEPS):
-        model.train_step(xs, ys)
-        if g1 is None:
-            g1 = model.grad.cpu().numpy() / model.world
-        params.append(model.flat.cpu().numpy().copy())
-    torch.cuda.synchronize()
-    return np.stack(params), g1, list(model.names)
+    P, _, g1 = DP.train_steps(model, xs, ys, STEPS, first_grad=True)
+    return P, g1 / model.world, list(model.names)
 
 
-def main():
-    import torch
-    import torch.distributed as dist
-    from cnn_graph_amd import dist as cdist
-    out = sys.argv[1]
-    rank, world, _ = cdist.init(backend="gloo")
-    dev = torch.device("cuda", 0)
-    torch.cuda.set_device(dev)
+def rank_result(rank, world, dev, comm):
     L, x, labels = problem()
-    lo, hi = cdist.shard(N_GLOBAL, rank, world)
-    comm = cdist.TorchComm()
-    res = {"world": world}
+    lo, hi = DP.shard_of(N_GLOBAL, rank, world)
+    res = {}
     for fn in INFER_FUNCS:
         P, g1, _ = run(fn, L, x[lo:hi], labels[lo:hi], dev, comm)
-        gathered = [torch.zeros(P.size, dtype=torch.float32) for _ in range(world)]
-        dist.all_gather(gathered, torch.from_numpy(P.reshape(-1)))
         res[f"{fn}_P"] = P
-        res[f"{fn}_P_r1"] = gathered[1].numpy().reshape(P.shape)
+        res[f"{fn}_P_r1"] = DP.gather_ranks(P)[1]
         res[f"{fn}_g1"] = g1
-    if rank == 0:
-        np.savez(out, **res)
-    dist.barrier()
-    dist.destroy_process_group()
-
-
-if __name__ == "__main__":
-    main()
+    return res

@@ -1,23 +1,14 @@
-"""Worker of tests/test_gpu_glstm_dp.py (not a test module): one rank of the
-data-parallel gconv-LSTM training step (gconv_lstm.GLSTMModel: glstm_layer +
-fc_layer + MSE + Adam, ONE all-reduce of the flat gradient bucket per step,
-grad_scale = 1/world) at config E's graph and shape (T = 12, K = 3, H = 32,
-Fin = 2), launched by ``torch.distributed.run --nproc-per-node 2``.  Both ranks
-share cuda:0 and exchange over gloo (dist.TorchComm; RCCL refuses two ranks on
-one GPU).  Rank r trains on its contiguous shard of a fixed global batch; rank
-0 writes both replicas' parameters after every step and the first step's
-exchanged gradient bucket for the parent to compare.
-
-  python -m torch.distributed.run --nproc-per-node 2 tests/glstm_dp_worker.py OUT.npz
-"""
-import os
-import sys
-
+"""Case of tests/test_gpu_glstm_dp.py (not a test module): the data-parallel
+gconv-LSTM training step (gconv_lstm.GLSTMModel: glstm_layer + fc_layer + MSE +
+Adam, ONE all-reduce of the flat gradient bucket per step, grad_scale = 1/world)
+at config E's graph and shape (T = 12, K = 3, H = 32, Fin = 2).  Rank r trains
+on its contiguous shard of a fixed global batch; rank 0 writes both replicas'
+parameters after every step and the first step's exchanged gradient bucket for
+the parent to compare.  Run through tests/dp_harness.py (case
+``glstm_dp_worker``)."""
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import dp_harness as DP
 
 STEPS = 3
 N_GLOBAL, T, FIN, H, K, FOUT = 8, 12, 2, 32, 3, 2
@@ -49,36 +40,12 @@ def run(L, x, labels, dev, comm, optimizer="adam"):
                        optimizer=optimizer, device=dev, seed=2017, comm=comm)
     xs = torch.from_numpy(np.ascontiguousarray(x)).to(dev)
     ys = torch.from_numpy(np.ascontiguousarray(labels)).to(dev)
-    params, losses, g1 = [], [], None
-    for i in range(STEPS):
-        loss = model.train_step(xs, ys)
-        if i == 0:
-            g1 = (model.grad / model.world).cpu().numpy().copy()
-        params.append(model.flat.cpu().numpy().copy())
-        losses.append(float(loss.item()))
-    torch.cuda.synchronize()
-    return np.stack(params), g1, np.array(losses)
+    P, losses, g1 = DP.train_steps(model, xs, ys, STEPS, first_grad=True)
+    return P, g1 / model.world, losses
 
 
-def main():
-    import torch
-    import torch.distributed as dist
-    from cnn_graph_amd import dist as cdist
-    out = sys.argv[1]
-    rank, world, _ = cdist.init(backend="gloo")
-    dev = torch.device("cuda", 0)
-    torch.cuda.set_device(dev)
+def rank_result(rank, world, dev, comm):
     L, x, labels = problem()
-    lo, hi = cdist.shard(N_GLOBAL, rank, world)
-    comm = cdist.TorchComm()
-    P, g1, losses = run(L, x[lo:hi], labels[lo:hi], dev, comm)
-    gathered = [torch.zeros(P.size, dtype=torch.float32) for _ in range(world)]
-    dist.all_gather(gathered, torch.from_numpy(P.reshape(-1)))
-    if rank == 0:
-        np.savez(out, P=P, P_r1=gathered[1].numpy().reshape(P.shape), g1=g1, world=world)
-    dist.barrier()
-    dist.destroy_process_group()
-
-
-if __name__ == "__main__":
-    main()
+    lo, hi = DP.shard_of(N_GLOBAL, rank, world)
+    P, g1, _ = run(L, x[lo:hi], labels[lo:hi], dev, comm)
+    return dict(P=P, P_r1=DP.gather_ranks(P)[1], g1=g1)

@@ -1,22 +1,12 @@
-"""Worker of tests/test_gpu_glstm_period.py::test_world2_over_gloo (not a test
-module): one rank of the data-parallel training step of
-glstm_period.GLSTMPeriodModel in both merge modes, launched by
-``torch.distributed.run --nproc-per-node 2``.  Both ranks share cuda:0 and
-exchange over gloo (dist.TorchComm), as tests/glstm_dp_worker.py does.  Rank r
-trains on its contiguous shard of a fixed global batch; rank 0 writes both
-replicas' parameters after every step, and every rank's wrapper seeds of a
-model built with dropout on.
-
-  python -m torch.distributed.run --nproc-per-node 2 tests/glstm_period_dp_worker.py OUT.npz
-"""
-import os
-import sys
-
+"""Case of tests/test_gpu_glstm_period.py::test_world2_over_gloo (not a test
+module): the data-parallel training step of glstm_period.GLSTMPeriodModel in
+both merge modes.  Rank r trains on its contiguous shard of a fixed global
+batch; rank 0 writes both replicas' parameters after every step, and every
+rank's wrapper seeds of a model built with dropout on.  Run through
+tests/dp_harness.py (case ``glstm_period_dp_worker``)."""
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import dp_harness as DP
 
 STEPS = 2
 N_GLOBAL, M, T, FIN, H, K, FOUT, LAYERS = 4, 40, (3, 2, 4), 2, 8, 2, 2, 2
@@ -45,44 +35,20 @@ def run(mode, L, x, labels, dev, comm):
     model = build(mode, L, x.shape[0], dev, comm)
     xs = torch.from_numpy(np.ascontiguousarray(x)).to(dev)
     ys = torch.from_numpy(np.ascontiguousarray(labels)).to(dev)
-    params = []
-    for _ in range(STEPS):
-        model.train_step(xs, ys)
-        params.append(model.flat.cpu().numpy().copy())
-    torch.cuda.synchronize()
-    return np.stack(params)
+    return DP.train_steps(model, xs, ys, STEPS)[0]
 
 
-def main():
-    import torch
-    import torch.distributed as dist
-    from cnn_graph_amd import dist as cdist
-    out = sys.argv[1]
-    rank, world, _ = cdist.init(backend="gloo")
-    dev = torch.device("cuda", 0)
-    torch.cuda.set_device(dev)
+def rank_result(rank, world, dev, comm):
     L, x, labels = problem()
-    lo, hi = cdist.shard(N_GLOBAL, rank, world)
-    comm = cdist.TorchComm()
-    res = {"world": world}
+    lo, hi = DP.shard_of(N_GLOBAL, rank, world)
+    res = {}
     for mode in MODES:
         P = run(mode, L, x[lo:hi], labels[lo:hi], dev, comm)
-        gathered = [torch.zeros(P.size, dtype=torch.float32) for _ in range(world)]
-        dist.all_gather(gathered, torch.from_numpy(P.reshape(-1)))
         # the mask-stream seeds of this rank's wrappers (dropout on), as int64 bit patterns
         dropped = build(mode, L, hi - lo, dev, comm, keep=0.8)
-        seeds = torch.tensor([w._seed - (1 << 64) if w._seed >= 1 << 63 else w._seed
-                              for ws in dropped.wrapped for w in ws], dtype=torch.int64)
-        all_seeds = [torch.zeros_like(seeds) for _ in range(world)]
-        dist.all_gather(all_seeds, seeds)
+        seeds = np.array([w._seed - (1 << 64) if w._seed >= 1 << 63 else w._seed
+                          for ws in dropped.wrapped for w in ws], dtype=np.int64)
         res[f"{mode}_P"] = P
-        res[f"{mode}_P_r1"] = gathered[1].numpy().reshape(P.shape)
-        res[f"{mode}_seeds"] = torch.stack(all_seeds).numpy()
-    if rank == 0:
-        np.savez(out, **res)
-    dist.barrier()
-    dist.destroy_process_group()
-
-
-if __name__ == "__main__":
-    main()
+        res[f"{mode}_P_r1"] = DP.gather_ranks(P)[1]
+        res[f"{mode}_seeds"] = np.stack(DP.gather_ranks(seeds))
+    return res

@@ -5,15 +5,11 @@ grad_scale = 1/world, and the L2 term added once, in the update after the
 exchange.  Bars: both replicas bitwise equal after every step; the parameters
 within 1e-5 (normwise) of the full-batch run's after each of 2 Momentum steps
 with regularization = 5e-2 -- a term added once per rank would double it."""
-import os
-import socket
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import cgcnn_dp_worker as Wk
+import dp_harness as DP
 from oracle import cheb_oracle as O
 
 torch = pytest.importorskip("torch")
@@ -29,30 +25,12 @@ def dev(built_lib):
 
 @pytest.mark.timeout(400)
 def test_cgcnn_dp_world2_matches_full_batch(dev, tmp_path):
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import cgcnn_dp_worker as Wk
-    out = tmp_path / "cgcnn_dp.npz"
-    env = dict(os.environ)
-    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    with socket.socket() as sk:
-        sk.bind(("127.0.0.1", 0))
-        port = sk.getsockname()[1]
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
-           "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "tests", "cgcnn_dp_worker.py"), str(out)]
-    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=360)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    d = np.load(out)
-    assert int(d["world"]) == 2
+    d = DP.launch_world2("cgcnn_dp_worker", tmp_path / "cgcnn_dp.npz", 360)
     assert np.array_equal(d["P"], d["P_r1"]), "replicas diverged"
     L, x, labels = Wk.problem()
     P, losses, (rb, rn) = Wk.run(L, x, labels, dev, None)
     assert np.all(np.isfinite(losses)) and np.all(np.isfinite(d["losses"]))
-    for n in range(Wk.STEPS):
-        if n:
-            assert not np.array_equal(d["P"][n], d["P"][n - 1])  # the update ran
-        err = O.normwise_err(d["P"][n], P[n].astype(np.float64))
-        assert err < 1e-5, (n + 1, err)
+    DP.assert_tracks_full_batch(d["P"], P, Wk.STEPS)
     # the bar sees the term: one step without it ends further away than the bar
     from cnn_graph_amd import CGCNNModel
     plain = CGCNNModel(L, Wk.N_GLOBAL, Wk.F, Wk.K, Wk.P, Wk.MFC, regularization=0.0, momentum=0.9,

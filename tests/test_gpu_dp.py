@@ -8,15 +8,11 @@ whole batch.  Bars: the exchanged gradient / world and the loss within 1e-5
 normwise of the full-batch ones, both replicas bitwise identical after three
 steps, and their parameters within 1e-4 of the full-batch run's (Adam's
 normalised step amplifies fp32 reduction-order differences)."""
-import os
-import socket
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import dp_harness as DP
+import dp_resgnn_worker as Wk
 from oracle import cheb_oracle as O
 
 torch = pytest.importorskip("torch")
@@ -32,20 +28,7 @@ def dev(built_lib):
 
 @pytest.mark.timeout(300)
 def test_resgnn_dp_world2_matches_full_batch(dev, tmp_path):
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import dp_resgnn_worker as Wk
-    out = tmp_path / "dp.npz"
-    env = dict(os.environ)
-    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    with socket.socket() as sk:
-        sk.bind(("127.0.0.1", 0))
-        port = sk.getsockname()[1]
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
-           "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "tests", "dp_resgnn_worker.py"), str(out)]
-    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    d = np.load(out)
+    d = DP.launch_world2("dp_resgnn_worker", tmp_path / "dp.npz", 240)
     L, x, labels = Wk.problem()
     losses, g1, flat = Wk.run(Wk.N_GLOBAL, x, labels, L, None, dev)
     assert np.array_equal(d["flat"], d["flat_r1"]), "replicas diverged"

@@ -10,13 +10,14 @@ at grad_scale 1/2.  Bars: both replicas bitwise equal after every step, and
 their weights within 1e-5 (normwise) of the full-batch runs' after 1, 2 and 3
 steps (lib/graph_model.py:296-298 is where the exchange sits)."""
 import os
-import socket
 import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+import dp_bench_worker as Wk
+import dp_harness as DP
 from conftest import ROOT
 from oracle import cheb_oracle as O
 
@@ -33,41 +34,22 @@ def dev(built_lib):
 
 @pytest.mark.timeout(300)
 def test_bench_schedule_world2_matches_full_batch(dev, tmp_path):
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import dp_bench_worker as Wk
-    out = tmp_path / "dpb.npz"
-    env = dict(os.environ)
-    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    with socket.socket() as sk:
-        sk.bind(("127.0.0.1", 0))
-        port = sk.getsockname()[1]
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
-           "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "tests", "dp_bench_worker.py"), str(out)]
-    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    d = np.load(out)
-    assert int(d["world"]) == 2
+    d = DP.launch_world2("dp_bench_worker", tmp_path / "dpb.npz", 240)
     assert np.array_equal(d["W"], d["W_r1"]), "replicas diverged"
     L, x, dy, W0 = Wk.problem()
     full_fused = Wk.run(x, dy, W0, L, dev, 1, None, "fused", grad_scale=0.5)
     full_unfused = Wk.run(x, dy, W0, L, dev, 1, None, "unfused", grad_scale=0.5)
     assert np.array_equal(full_fused, full_unfused)  # the fused update is k_adam's, bitwise
-    for n in range(Wk.STEPS):
-        assert not np.array_equal(d["W"][n], W0)
-        err = O.normwise_err(d["W"][n], full_fused[n].astype(np.float64))
-        assert err < 1e-5, (n + 1, err)
+    DP.assert_tracks_full_batch(d["W"], full_fused, Wk.STEPS, start=W0)
 
 
 def _bench_json(args, timeout=400):
     """Run bench.py as the driver does (no WORLD_SIZE: bench.py starts its own
     torchrun child) and return its one JSON line."""
     import json
-    env = {k: v for k, v in os.environ.items()
-           if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + args
-    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout)
+    r = subprocess.run(cmd, env=DP.child_env(strip_launcher_vars=True), capture_output=True, text=True,
+                       timeout=timeout)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout[-3000:]

@@ -5,15 +5,11 @@ three-branch flat buffer with merge_layer carved last included.  Bars: both
 replicas bitwise equal after every step; the first step's exchanged gradient
 (sum / 2) within 1e-5 (normwise) of the one-process full batch's, and the
 parameters within 1e-5 of the full-batch run's after each of 3 Adam steps."""
-import os
-import socket
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import dp_harness as DP
+import gconv_net_dp_worker as Wk
 from oracle import cheb_oracle as O
 
 torch = pytest.importorskip("torch")
@@ -29,21 +25,7 @@ def dev(built_lib):
 
 @pytest.mark.timeout(300)
 def test_gconv_net_world2_matches_full_batch(dev, tmp_path):
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import gconv_net_dp_worker as Wk
-    out = tmp_path / "gconv_net_dp.npz"
-    env = dict(os.environ)
-    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    with socket.socket() as sk:
-        sk.bind(("127.0.0.1", 0))
-        port = sk.getsockname()[1]
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
-           "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "tests", "gconv_net_dp_worker.py"), str(out)]
-    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=280)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    d = np.load(out)
-    assert int(d["world"]) == 2
+    d = DP.launch_world2("gconv_net_dp_worker", tmp_path / "gconv_net_dp.npz", 280)
     L, x, labels = Wk.problem()
     for fn in Wk.INFER_FUNCS:
         assert np.array_equal(d[f"{fn}_P"], d[f"{fn}_P_r1"]), f"{fn}: replicas diverged"
@@ -54,9 +36,4 @@ def test_gconv_net_world2_matches_full_batch(dev, tmp_path):
         e_g = O.normwise_err(d[f"{fn}_g1"], g1.astype(np.float64))
         print(f"{fn}: first exchanged gradient, normwise err {e_g:.3e}")
         assert e_g < 1e-5, (fn, e_g)
-        for n in range(Wk.STEPS):
-            if n:
-                assert not np.array_equal(d[f"{fn}_P"][n], d[f"{fn}_P"][n - 1])  # the update ran
-            err = O.normwise_err(d[f"{fn}_P"][n], P[n].astype(np.float64))
-            print(f"{fn} step {n + 1}: normwise err {err:.3e}")
-            assert err < 1e-5, (fn, n + 1, err)
+        DP.assert_tracks_full_batch(d[f"{fn}_P"], P, Wk.STEPS)

@@ -11,15 +11,11 @@ per rank; one process trains on the whole 8-sample batch.  Bars: both replicas
 bitwise equal after every step; the first step's exchanged gradient (sum / 2)
 within 1e-5 (normwise) of the full batch's, and the parameters within 1e-5 of
 the full-batch run's after each of 3 Adam steps."""
-import os
-import socket
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import dp_harness as DP
+import glstm_dp_worker as Wk
 from oracle import cheb_oracle as O
 
 torch = pytest.importorskip("torch")
@@ -35,31 +31,13 @@ def dev(built_lib):
 
 @pytest.mark.timeout(400)
 def test_glstm_dp_world2_matches_full_batch(dev, tmp_path):
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import glstm_dp_worker as Wk
-    out = tmp_path / "glstm_dp.npz"
-    env = dict(os.environ)
-    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    with socket.socket() as sk:
-        sk.bind(("127.0.0.1", 0))
-        port = sk.getsockname()[1]
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
-           "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "tests", "glstm_dp_worker.py"), str(out)]
-    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=360)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    d = np.load(out)
-    assert int(d["world"]) == 2
+    d = DP.launch_world2("glstm_dp_worker", tmp_path / "glstm_dp.npz", 360)
     assert np.array_equal(d["P"], d["P_r1"]), "replicas diverged"
     L, x, labels = Wk.problem()
     P, g1, losses = Wk.run(L, x, labels, dev, None)
     assert np.all(np.isfinite(losses))
     assert O.normwise_err(d["g1"], g1.astype(np.float64)) < 1e-5
-    for n in range(Wk.STEPS):
-        if n:
-            assert not np.array_equal(d["P"][n], d["P"][n - 1])  # the update ran
-        err = O.normwise_err(d["P"][n], P[n].astype(np.float64))
-        assert err < 1e-5, (n + 1, err)
+    DP.assert_tracks_full_batch(d["P"], P, Wk.STEPS)
 
 
 def test_glstm_model_flat_bucket_and_optimizers(dev):
@@ -68,8 +46,6 @@ def test_glstm_model_flat_bucket_and_optimizers(dev):
     config E; the fc output shape; sgd / rmsprop run and move the weights by
     their own rules (one step from the same start: sgd moves by lr * g,
     rmsprop by lr * g / sqrt(0.1 g^2 + 0.9 + 1e-10))."""
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import glstm_dp_worker as Wk
     from cnn_graph_amd.gconv_lstm import GLSTMModel
     L, x, labels = Wk.problem()
     x, labels = x[:2], labels[:2]
@@ -104,8 +80,6 @@ def test_glstm_dropout_reproducible_from_seed(dev):
     models built with one seed train bitwise identically whatever was built
     before them in the process, another seed (or another rank) draws other
     masks, and the masks really drop (the step differs from keep_prob = 1)."""
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import glstm_dp_worker as Wk
     from cnn_graph_amd.gconv_lstm import GLSTMModel, dropout_seed
     L, x, labels = Wk.problem()
     xs, ys = torch.from_numpy(x[:2]).to(dev), torch.from_numpy(labels[:2]).to(dev)

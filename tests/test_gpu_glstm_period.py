@@ -8,18 +8,14 @@ ReLU head needs no special care here, as in tests/test_gpu_glstm_gconv.py: the
 normwise measure weighs a flipped pre-activation of size ~1e-7 against the
 largest entry.  Shapes: ring-with-chords graphs of M = 17 and 40, N = 3,
 T = (3, 2, 4) (unequal on purpose)."""
-import os
-import socket
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
+import dp_harness as DP
 import fourier_edge_cases as FE
 import glstm_gconv_ref as GR
+import glstm_period_dp_worker as Wk
 import glstm_period_ref as PR
-from conftest import ROOT
 from oracle import cheb_oracle as O
 
 torch = pytest.importorskip("torch")
@@ -288,29 +284,12 @@ def test_world2_over_gloo(dev, tmp_path):
     within 1e-5 of the one-process full batch (keep_prob 1: the ranks' masks
     differ by design, so a dropped run has no full-batch equal); with dropout
     on, the ranks' wrappers draw distinct masks."""
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import glstm_period_dp_worker as Wk
-    out = tmp_path / "period_dp.npz"
-    env = dict(os.environ)
-    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    with socket.socket() as sk:
-        sk.bind(("127.0.0.1", 0))
-        port = sk.getsockname()[1]
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
-           "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "tests", "glstm_period_dp_worker.py"), str(out)]
-    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=280)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    d = np.load(out)
-    assert int(d["world"]) == 2
+    d = DP.launch_world2("glstm_period_dp_worker", tmp_path / "period_dp.npz", 280)
     for mode in Wk.MODES:
         assert np.array_equal(d[f"{mode}_P"], d[f"{mode}_P_r1"]), f"{mode}: replicas diverged"
         L, x, labels = Wk.problem()
         P = Wk.run(mode, L, x, labels, dev, None)
-        assert not np.array_equal(d[f"{mode}_P"][0], d[f"{mode}_P"][1])  # the second update ran
-        for n in range(Wk.STEPS):
-            err = O.normwise_err(d[f"{mode}_P"][n], P[n].astype(np.float64))
-            print(f"{mode} step {n + 1}: normwise err {err:.3e}")
-            assert err <= 1e-5, (mode, n + 1, err)
+        print(mode)
+        DP.assert_tracks_full_batch(d[f"{mode}_P"], P, Wk.STEPS)  # the second update ran, too
         seeds = d[f"{mode}_seeds"]  # [rank][wrapper]
         assert len(set(seeds.reshape(-1).tolist())) == seeds.size == 2 * 3 * Wk.LAYERS
