@@ -123,7 +123,7 @@ def _supported(entry, *args) -> bool:
     return bool(ok.value)
 
 
-ACTS = {"none": _lib.CG_ACT_NONE, "relu": _lib.CG_ACT_RELU, "tanh": _lib.CG_ACT_TANH}
+ACTS = _lib.enum_names("CG_ACT_")
 
 
 def act_forward_(y: torch.Tensor, residual: torch.Tensor | None = None, act: str = "none"):
@@ -190,23 +190,37 @@ def cheb_forward(plan: ChebPlan, x: torch.Tensor, W: torch.Tensor | None, K: int
     return basis, y
 
 
-def cheb_backward(plan: ChebPlan, dy: torch.Tensor, basis: torch.Tensor, W: torch.Tensor, K: int,
-                  need_dx: bool = True, need_dW: bool = True, layout: str = "rows"):
-    """(dx [N,M,Fin] or None, dW [Fin*K, Fout] or None); layout: the forward's."""
+def _cheb_backward(plan, dy, y, act, basis, W, K, dx, dx_accumulate, need_dx, need_dW, layout,
+                   want_dz):
+    """The body of cheb_backward (y None, act 'none', no dz: the C side then
+    makes no copy of dy) and cheb_backward_ex: (dx, dW, dz)."""
     _check_dev("dy", dy)
     dy = dy.contiguous()
     N, M, Fout = dy.shape
     FinK = int(W.shape[0])
     Fin = FinK // K
     dev = dy.device
-    dx = torch.empty((N, M, Fin), device=dev, dtype=torch.float32) if need_dx else None
+    if dx is not None:
+        _check_out("dx", dx, (N, M, Fin))
+    elif need_dx:
+        if dx_accumulate:
+            raise ValueError("dx_accumulate needs a dx tensor")
+        dx = torch.empty((N, M, Fin), device=dev, dtype=torch.float32)
     dW = torch.empty((FinK, Fout), device=dev, dtype=torch.float32) if need_dW else None
+    dz = torch.empty((N, M, Fout), device=dev, dtype=torch.float32) if want_dz else None
     _, bwd_ws = plan.workspace_bytes(N, Fin, K, Fout)
     ws, s = _plan_ws(plan, bwd_ws, dy)
-    _lib.call("cg_cheb_backward_layout", plan.handle, N, Fin, K, Fout, _p(dy), None,
-              _lib.CG_ACT_NONE, _lib.BASIS_LAYOUTS[layout], _p(basis), _p(W.contiguous()), _p(dx),
-              0, _p(dW), None, _p(ws), bwd_ws, s)
-    return dx, dW
+    _lib.call("cg_cheb_backward_layout", plan.handle, N, Fin, K, Fout, _p(dy), _p(y), ACTS[act],
+              _lib.BASIS_LAYOUTS[layout], _p(basis), _p(W.contiguous()),
+              _p(dx if need_dx else None), int(dx_accumulate), _p(dW), _p(dz), _p(ws), bwd_ws, s)
+    return (dx if need_dx else None), dW, dz
+
+
+def cheb_backward(plan: ChebPlan, dy: torch.Tensor, basis: torch.Tensor, W: torch.Tensor, K: int,
+                  need_dx: bool = True, need_dW: bool = True, layout: str = "rows"):
+    """(dx [N,M,Fin] or None, dW [Fin*K, Fout] or None); layout: the forward's."""
+    return _cheb_backward(plan, dy, None, "none", basis, W, K, None, False, need_dx, need_dW,
+                          layout, want_dz=False)[:2]
 
 
 def cheb_backward_ex(plan: ChebPlan, dy: torch.Tensor, y: torch.Tensor | None, act: str,
@@ -216,26 +230,8 @@ def cheb_backward_ex(plan: ChebPlan, dy: torch.Tensor, y: torch.Tensor | None, a
     """Backward through y = act(basis W + residual): returns (dx, dW, dz) where
     dz = dy * act'(y) is also the gradient of the residual input.  With
     dx_accumulate the input gradient is added into the given ``dx``."""
-    _check_dev("dy", dy)
-    dy = dy.contiguous()
-    N, M, Fout = dy.shape
-    FinK = int(W.shape[0])
-    Fin = FinK // K
-    dev = dy.device
-    if need_dx and dx is None:
-        if dx_accumulate:
-            raise ValueError("dx_accumulate needs a dx tensor")
-        dx = torch.empty((N, M, Fin), device=dev, dtype=torch.float32)
-    if dx is not None:
-        _check_out("dx", dx, (N, M, Fin))
-    dW = torch.empty((FinK, Fout), device=dev, dtype=torch.float32) if need_dW else None
-    dz = torch.empty((N, M, Fout), device=dev, dtype=torch.float32)
-    _, bwd_ws = plan.workspace_bytes(N, Fin, K, Fout)
-    ws, s = _plan_ws(plan, bwd_ws, dy)
-    _lib.call("cg_cheb_backward_layout", plan.handle, N, Fin, K, Fout, _p(dy), _p(y), ACTS[act],
-              _lib.BASIS_LAYOUTS[layout], _p(basis), _p(W.contiguous()),
-              _p(dx if need_dx else None), int(dx_accumulate), _p(dW), _p(dz), _p(ws), bwd_ws, s)
-    return (dx if need_dx else None), dW, dz
+    return _cheb_backward(plan, dy, y, act, basis, W, K, dx, dx_accumulate, need_dx, need_dW,
+                          layout, want_dz=True)
 
 
 def mse_loss(pred: torch.Tensor, labels: torch.Tensor, need_grad: bool = True):
@@ -628,7 +624,7 @@ def bias_grad(dy: torch.Tensor, out: torch.Tensor | None = None, accumulate: boo
     return out
 
 
-LSTM_GATES = {"reference": 0, "standard": 1}
+LSTM_GATES = _lib.enum_names("CG_LSTM_GATES_")
 
 
 def _cell_outs(out_c, out_h, out_act, lead, R: int, H: int, dev):
@@ -1168,9 +1164,6 @@ def class_xent(logits, labels):
 
 
 # -- bias + activation (lib/graph_conv.py:178-199, fc :220-226) --------------------
-BIAS_ACTS = {"none": _lib.CG_ACT_NONE, "relu": _lib.CG_ACT_RELU, "tanh": _lib.CG_ACT_TANH}
-
-
 class _BiasAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, bias, act: str):
@@ -1185,7 +1178,7 @@ class _BiasAct(torch.autograd.Function):
             if n % blen:
                 raise ValueError(f"bias of {blen} elements does not tile x of {n}")
         y = torch.empty_like(x)
-        _lib.call("cg_bias_act_forward", n, blen, _p(x), _p(bias), BIAS_ACTS[act], _p(y), _stream(x))
+        _lib.call("cg_bias_act_forward", n, blen, _p(x), _p(bias), ACTS[act], _p(y), _stream(x))
         ctx.save_for_backward(y)
         ctx.act, ctx.blen, ctx.has_bias = act, blen, bias is not None
         ctx.bshape = None if bias is None else tuple(bias.shape)
@@ -1202,7 +1195,7 @@ class _BiasAct(torch.autograd.Function):
         if ctx.has_bias and ctx.needs_input_grad[1]:
             db = torch.empty(ctx.bshape, device=dy.device, dtype=torch.float32)
             ws, nb = _workspace("cg_bias_act_workspace_bytes", n, ctx.blen, device=dy.device)
-        _lib.call("cg_bias_act_backward", n, ctx.blen, _p(dy), _p(y), BIAS_ACTS[ctx.act], _p(dz), _p(db),
+        _lib.call("cg_bias_act_backward", n, ctx.blen, _p(dy), _p(y), ACTS[ctx.act], _p(dz), _p(db),
                   0, _p(ws), nb, _stream(dy))
         return dz, db, None
 

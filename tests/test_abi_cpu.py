@@ -5,7 +5,7 @@ import ctypes
 import numpy as np
 import pytest
 
-from cnn_graph_amd import _lib
+from cnn_graph_amd import _lib, ops
 
 
 def test_library_exports_every_header_symbol(built_lib):
@@ -206,17 +206,114 @@ def test_forward_adam_validates(built_lib):
 
 def test_header_enums_match_the_binding(built_lib):
     """The ctypes binding's constants are the header's (basis layouts, paths,
-    variants, activations, status codes)."""
+    variants, activations, status codes, options, gate sets): every CG_* name
+    the binding exports, against this test's own reading of the header."""
     import re
-    from cnn_graph_amd import _lib
-    text = open(_lib.HEADER_PATH).read()
-    consts = {m.group(1): int(m.group(2)) for m in re.finditer(r"\b(CG_[A-Z_]+)\s*=\s*(-?\d+)", text)}
+    # comments go first: they hold text like "CG_OPT_GEMM_X3 = 0" about option VALUES
+    text = re.sub(r"/\*.*?\*/", " ", open(_lib.HEADER_PATH).read(), flags=re.S)
+    consts = {m.group(1): int(m.group(2)) for m in re.finditer(r"\b(CG_[A-Z0-9_]+)\s*=\s*(-?\d+)", text)}
     for name in ("CG_BASIS_ROWS", "CG_BASIS_ORDERS", "CG_BASIS_PLANES", "CG_PATH_AUTO",
                  "CG_PATH_RESIDENT", "CG_PATH_STREAM", "CG_ACT_NONE", "CG_ACT_RELU"):
         assert name in consts, name
         assert getattr(_lib, name) == consts[name], name
     assert _lib.BASIS_LAYOUTS == {"rows": consts["CG_BASIS_ROWS"], "orders": consts["CG_BASIS_ORDERS"],
                                   "planes": consts["CG_BASIS_PLANES"]}
+    exported = [n for n in vars(_lib) if n.startswith("CG_")]
+    assert set(exported) == set(consts)
+    for name in exported:
+        assert getattr(_lib, name) == consts[name], name
+    assert [consts[n] for n in ("CG_OK", "CG_ERR_ARG", "CG_ERR_HIP", "CG_ERR_UNSUPPORTED",
+                                "CG_ERR_ALLOC", "CG_ERR_COMM")] == list(range(6))
+
+    def by_prefix(prefix):
+        return {n[len(prefix):].lower(): v for n, v in consts.items() if n.startswith(prefix)}
+    assert _lib.PATHS == by_prefix("CG_PATH_") == {"auto": 0, "resident": 1, "stream": 2}
+    assert ops.ACTS == by_prefix("CG_ACT_") == {"none": 0, "relu": 1, "tanh": 2}
+    assert ops.LSTM_GATES == by_prefix("CG_LSTM_GATES_") == {"reference": 0, "standard": 1}
+    assert not hasattr(ops, "BIAS_ACTS")
+    # the prefix rule against the dicts that were written out by hand before it
+    assert _lib.OPTIONS == {"dw_direct": 0, "dw_w2": 1, "dw_waves": 2, "spmm_pw": 3, "grp16": 4,
+                            "grp_pc": 5, "clen_dy": 6, "seq_xpre": 7, "dw_x3": 8, "gemm_x3": 9,
+                            "mfma_stagger": 10}
+    assert len(_lib.OPTIONS) == consts["CG_OPT_COUNT"]
+    assert _lib.VARIANTS == {"auto": 0, "classic": 1, "unfused_dw": 2, "narrow": 3, "steps": 4}
+
+
+def _old_header_symbols(path):
+    """header_symbols as it was before the prototypes were parsed: names only."""
+    import re
+    return sorted(set(re.findall(r"^\s*(?:const\s+)?\w+\s*\*?\s*(cg_\w+)\s*\(", open(path).read(), re.M)))
+
+
+def test_every_prototype_maps():
+    """Both headers parse to the names the name-only scan finds, every type has
+    a ctypes type, and each entry has as many argtypes as the header has
+    parameters."""
+    protos = {}
+    for path in (_lib.HEADER_PATH, _lib.TESTING_HEADER_PATH):
+        got = _lib.header_prototypes(path)
+        assert sorted(got) == _lib.header_symbols(path) == _old_header_symbols(path)
+        assert not set(got) & set(protos)
+        protos.update(got)
+    assert len(protos) == 102
+    sigs = _lib.signatures(_lib.HEADER_PATH, _lib.TESTING_HEADER_PATH)
+    assert sigs == _lib._SIGNATURES and len(_lib._SIGNATURES) == len(protos)
+    for name, (ret, params) in protos.items():
+        argtypes, restype = _lib._SIGNATURES[name]
+        assert len(argtypes) == len(params), name
+        assert restype is (ctypes.c_char_p if name == "cg_last_error" else ctypes.c_int), name
+    assert protos["cg_version"] == ("int", [])
+    assert protos["cg_branch_merge_backward"][1][5:9] == ["const float* const*"] * 2 + ["float* const*"] * 2
+    assert protos["cg_plan_query_stream_dispatch"][1][-2:] == ["int", "int32_t[16]"]
+    assert protos["cg_comm_init"][1] == ["cg_comm**", "int", "int", "const unsigned char[128]", "int"]
+
+
+@pytest.mark.parametrize("decl", ["int cg_x(long double v);", "int cg_x(int32_t n, double v);",
+                                  "long cg_x(void);"])
+def test_unknown_types_are_refused(tmp_path, decl):
+    """A type outside the binding's tables is an error that names the function:
+    nothing falls back to a default."""
+    path = tmp_path / "x.h"
+    path.write_text(decl + "\n")
+    assert _lib.header_symbols(str(path)) == ["cg_x"]
+    with pytest.raises(ValueError, match="cg_x"):
+        _lib.signatures(str(path))
+
+
+def test_pinned_signatures():
+    """Argument lists written out by hand from the headers: every scalar kind,
+    the typed host out-pointers, the pointer arrays and the array parameter."""
+    i, i32, i64, sz = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t
+    f, u64, vp = ctypes.c_float, ctypes.c_uint64, ctypes.c_void_p
+    P = ctypes.POINTER
+    pinned = {
+        "cg_last_error": ([], ctypes.c_char_p),
+        "cg_plan_create": ([P(vp), i, i32, i64, vp, vp, vp, vp, vp, vp], i),
+        "cg_cheb_workspace_bytes": ([vp, i32, i32, i32, i32, P(sz), P(sz)], i),
+        "cg_cheb_forward_adam": ([vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, f, f, f, f, i32, f,
+                                  vp, vp, vp, i32, vp, vp, vp, sz, vp], i),
+        "cg_cheb_basis_elems": ([vp, i32, i32, i32, i32, i32, P(i64)], i),
+        "cg_weight_grad_planes": ([i64, i32, i32, i32, vp, i64, vp, vp, i32, vp, sz, vp], i),
+        "cg_fres_forward_drop": ([i32, i32, i32, i32, vp, sz, vp, vp, f, u64, vp, i32, vp, vp, vp,
+                                  sz, vp], i),
+        "cg_concat_drop_forward": ([i32, i32, i32, vp, vp, f, vp, vp, vp], i),
+        "cg_branch_merge_backward": ([i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp], i),
+        "cg_plan_query_stream_dispatch": ([vp, i32, i32, i32, i32, i, vp], i),
+        "cg_graclus_match_f64": ([i64, vp, vp, vp, i32, vp, vp, vp, vp], i),
+    }
+    assert len(pinned["cg_cheb_forward_adam"][0]) == 25
+    for name, (argtypes, restype) in pinned.items():
+        got_args, got_res = _lib._SIGNATURES[name]
+        assert got_res is restype, name
+        assert [t.__name__ for t in got_args] == [t.__name__ for t in argtypes], name
+        assert all(a is b for a, b in zip(got_args, argtypes)), name
+    # a typed out-pointer still rejects the wrong byref; a void* takes what callers pass
+    assert P(sz).from_param(ctypes.byref(sz()))
+    with pytest.raises(TypeError):
+        _lib._SIGNATURES["cg_cheb_workspace_bytes"][0][5].from_param(ctypes.byref(ctypes.c_float()))
+    for v in (None, 4096, ctypes.byref(i32()), (vp * 2)(), (i32 * 16)(), b"x" * 128,
+              ctypes.create_string_buffer(128), _i32([1, 2])):
+        vp.from_param(v)
 
 
 def test_update_rule_validation(built_lib):
