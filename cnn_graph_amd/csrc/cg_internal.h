@@ -149,7 +149,7 @@ struct SlotLayout {
 struct ResidentFwdArgs {
   int M, Fin, K, Fout, Mp, dbg;
   const float* res;  // y epilogue: y = act(basis W + res) (res may be NULL)
-  int act;           // 0 = none, 1 = ReLU, 2 = tanh (cg::gate_tanh)
+  int act;           // CG_ACT_* (tanh: cg::gate_tanh)
   SlotLayout E;                        // L~
   const int* col;                      // CSR columns / values of L~ (tails)
   const float* val;
@@ -217,7 +217,7 @@ FastGeom fast_geometry(int M, int P, int max_row_nnz, int max_row_nnzT, int Fin,
 struct FastFwdArgs {
   int M, Fin, K, Fout, dbg;
   const float* res;  // y epilogue: y = act(basis W + res) (res may be NULL)
-  int act;           // 0 = none, 1 = ReLU, 2 = tanh (cg::gate_tanh)
+  int act;           // CG_ACT_* (tanh: cg::gate_tanh)
   FastImage E;  // L~
   const float* x;
   const float* W;
@@ -386,7 +386,7 @@ hipError_t launch_grp_clen_dy(const int* trowptr, const int* tcol, const float* 
 // C[p*c_plane + r*ldc + j] = sum_k A[r*lda + k] * B[p*bs_p + k*bs_k + j*bs_j],
 // r < R, k < Kc, j < Nc.  rowgemm_ok says whether the shape is supported.
 bool rowgemm_ok(int Kc, int lda, int Nc);
-// Epilogue (planes == 1 use): C = act(C + res), res [R][ldc] or NULL, act 1 = ReLU, 2 = tanh.
+// Epilogue (planes == 1 use): C = act(C + res), res [R][ldc] or NULL, act CG_ACT_*.
 // pfin > 0 (planes == 1, no epilogue): one pass over A computes Nc = P*pfin
 // columns, column jj being column jj % pfin of plane jj / pfin (B and C alike),
 // so A is read once for all planes instead of once per plane.
@@ -432,13 +432,13 @@ hipError_t launch_reduce_slabs_acc(const float* slab, int nslab, int64_t count, 
                                    int accumulate, hipStream_t s);
 
 // ---- elementwise epilogues and the MSE loss (epilogue.hip) ---------------------
-// y = act(y + res) in place (res may be NULL); act 1 = ReLU, 2 = tanh
+// y = act(y + res) in place (res may be NULL); act CG_ACT_*
 hipError_t launch_act_fwd(float* y, const float* res, int act, int64_t n, hipStream_t s);
-// dz = dy * act'(y) given the epilogue's output y (act 1: ReLU, dz = y > 0 ? dy : 0;
-// act 2: tanh, dz = dy (1 - y*y))
+// dz = dy * act'(y) given the epilogue's output y (CG_ACT_RELU: dz = y > 0 ? dy : 0;
+// CG_ACT_TANH: dz = dy (1 - y*y))
 hipError_t launch_act_bwd(const float* dy, const float* y, int act, float* dz, int64_t n,
                           hipStream_t s);
-// y = act(x + bias[i % blen]) (bias may be NULL); act 0 none, 1 ReLU, 2 tanh
+// y = act(x + bias[i % blen]) (bias may be NULL); act CG_ACT_*
 hipError_t launch_bias_act_fwd(const float* x, const float* bias, int64_t blen, int act, int64_t n,
                                float* y, hipStream_t s);
 // dz = dy * act'(y) given the activation's output y

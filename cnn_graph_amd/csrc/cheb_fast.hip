@@ -2,6 +2,7 @@
 // instantiations are compiled separately from cheb_fast_inst.hip).
 #include <algorithm>
 
+#include "../../include/cheb_mi355.h"  // CG_ACT_*
 #include "cg_internal.h"
 
 namespace cg {
@@ -33,7 +34,7 @@ FastGeom fast_geometry(int M, int P, int max_row_nnz, int max_row_nnzT, int Fin,
 }
 
 namespace {
-// TH: the tanh instantiations (act == 2), apart from the none / ReLU ones
+// TH: the tanh instantiations (act == CG_ACT_TANH), apart from the none / ReLU ones
 template <bool TH>
 hipError_t fast_forward_t(const FastGeom& g, int N, const FastFwdArgs& a, hipStream_t s) {
   // orders-layout basis: Fin <= 2 (cheb_abi.cpp::check_layout)
@@ -50,7 +51,7 @@ hipError_t fast_forward_t(const FastGeom& g, int N, const FastFwdArgs& a, hipStr
 }  // namespace
 
 hipError_t launch_fast_forward(const FastGeom& g, int N, const FastFwdArgs& a, hipStream_t s) {
-  return a.act == 2 ? fast_forward_t<true>(g, N, a, s) : fast_forward_t<false>(g, N, a, s);
+  return a.act == CG_ACT_TANH ? fast_forward_t<true>(g, N, a, s) : fast_forward_t<false>(g, N, a, s);
 }
 
 hipError_t launch_fast_backward(const FastGeom& g, int N, const FastBwdArgs& a, hipStream_t s) {

@@ -48,9 +48,9 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "act.h"
 #include "cg_internal.h"
 #include "launch.h"
-#include "lstm_gates.h"
 #include "split_bf16.h"
 
 namespace cg {
@@ -491,8 +491,8 @@ __global__ __launch_bounds__(kT) void cheb_fwd_fast(FastFwdArgs A) {
             if (m < M && f < Fout) {
               float v = c.acc[t][q][e];
               if (A.res) v = v + A.res[size_t(n) * M * Fout + size_t(m) * Fout + f];
-              if (TH) v = gate_tanh(v);
-              else if (A.act) v = v > 0.f ? v : 0.f;
+              if (TH) v = act_tanh(v);
+              else if (A.act != CG_ACT_NONE) v = act_relu(v);
               yn[size_t(m) * Fout + f] = v;
             }
           }

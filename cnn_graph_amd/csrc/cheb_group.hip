@@ -34,7 +34,7 @@
 #include "cg_internal.h"
 #include "launch.h"
 #include "lds_spmm.h"
-#include "lstm_gates.h"
+#include "act.h"
 
 namespace cg {
 namespace {
@@ -407,8 +407,8 @@ __global__ __launch_bounds__(256) void k_grp_yred(const float* __restrict__ yp, 
     float s = yp[i];
     for (int gg = 1; gg < G; ++gg) s = s + yp[int64_t(gg) * n + i];
     if (res) s = s + res[i];
-    if (act == 1) s = s > 0.f ? s : 0.f;
-    else if (act == 2) s = gate_tanh(s);
+    if (act == CG_ACT_RELU) s = act_relu(s);
+    else if (act == CG_ACT_TANH) s = act_tanh(s);
     y[i] = s;
   }
 }
@@ -428,11 +428,8 @@ __global__ __launch_bounds__(256) void k_grp_yred4(const float4* __restrict__ yp
       const float4 r = res[i];
       s = make_float4(s.x + r.x, s.y + r.y, s.z + r.z, s.w + r.w);
     }
-    if (act == 1)
-      s = make_float4(s.x > 0.f ? s.x : 0.f, s.y > 0.f ? s.y : 0.f, s.z > 0.f ? s.z : 0.f,
-                      s.w > 0.f ? s.w : 0.f);
-    else if (act == 2)
-      s = make_float4(gate_tanh(s.x), gate_tanh(s.y), gate_tanh(s.z), gate_tanh(s.w));
+    if (act == CG_ACT_RELU) s = act_relu(s);
+    else if (act == CG_ACT_TANH) s = act_tanh(s);
     y[i] = s;
   }
 }

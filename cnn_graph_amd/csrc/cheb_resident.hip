@@ -45,7 +45,7 @@
 
 #include "cg_internal.h"
 #include "launch.h"
-#include "lstm_gates.h"
+#include "act.h"
 
 namespace cg {
 namespace {
@@ -252,9 +252,7 @@ __global__ __launch_bounds__(kT) void cheb_fwd_resident(ResidentFwdArgs A) {
             if (m < M && f < Fout) {
               float v = acc[t][q][r];
               if (A.res) v = v + A.res[size_t(n) * M * Fout + size_t(m) * Fout + f];
-              if (A.act == 2) v = gate_tanh(v);
-              else if (A.act) v = v > 0.f ? v : 0.f;
-              yn[size_t(m) * Fout + f] = v;
+              yn[size_t(m) * Fout + f] = act_fwd(v, A.act);
             }
           }
         }

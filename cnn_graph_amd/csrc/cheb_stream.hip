@@ -22,7 +22,7 @@
 // the basis is bit-identical to the resident path and to lib/graph.py::chebyshev.
 #include "cg_internal.h"
 #include "launch.h"
-#include "lstm_gates.h"
+#include "act.h"
 #include "split_bf16.h"
 
 #include <algorithm>
@@ -407,9 +407,7 @@ __global__ __launch_bounds__(256) void k_rowgemm(RowGemmArgs a) {
         if (rr < a.R) {
           float v = acc[t][q];
           if (a.res) v = v + a.res[rr * a.ldc + col];
-          if (a.act == 2) v = gate_tanh(v);
-          else if (a.act) v = v > 0.f ? v : 0.f;
-          Cp[rr * a.ldc + col] = v;
+          Cp[rr * a.ldc + col] = act_fwd(v, a.act);
         }
       }
     }
@@ -515,9 +513,7 @@ __global__ __launch_bounds__(256) void k_rowgemm_x3(RowGemmArgs a) {
         if (rr < a.R) {
           float v = acc[t][q];
           if (a.res) v = v + a.res[rr * a.ldc + col];
-          if (a.act == 2) v = gate_tanh(v);
-          else if (a.act) v = v > 0.f ? v : 0.f;
-          Cp[rr * a.ldc + col] = v;
+          Cp[rr * a.ldc + col] = act_fwd(v, a.act);
         }
       }
     }

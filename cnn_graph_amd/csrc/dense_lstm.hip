@@ -7,6 +7,7 @@
 //   a   = (gx_t + h_{t-1} Wh) + bias
 //   c_t = c_{t-1} * sigmoid(a_f + forget_bias) + sigmoid(a_i) * tanh(a_j)
 //   h_t = tanh(c_t) * sigmoid(a_o)
+// (another cell than lstm_gates.h's lstm_cell_fwd: its own expressions stay here)
 // k_dlstm_bwd: the whole BPTT, t = T-1 .. 0: dh = dhs_t + dh_rec, the gate
 // backward from act and cs, dpre_t stored, dh_rec = dpre_t Wh^T.
 //

@@ -25,8 +25,8 @@
 //               ||t|| from a fixed-order sum of squares, non-finite t' flagged
 // The fast resident forward and the streaming row GEMM apply the residual /
 // ReLU / tanh epilogue in their own y store; these kernels are the fallback.
+#include "act.h"
 #include "cg_internal.h"
-#include "lstm_gates.h"
 
 namespace cg {
 namespace {
@@ -41,9 +41,7 @@ __global__ __launch_bounds__(256) void k_act_fwd(float* __restrict__ y, const fl
   for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n; i += int64_t(gridDim.x) * 256) {
     float v = y[i];
     if (res) v = v + res[i];
-    if (act == 2) v = gate_tanh(v);
-    else if (act) v = v > 0.f ? v : 0.f;
-    y[i] = v;
+    y[i] = act_fwd(v, act);
   }
 }
 
@@ -110,32 +108,24 @@ __global__ __launch_bounds__(1024) void k_clip_norm(float* __restrict__ t, int64
   if (tid == 0 && bad && nonfinite) *nonfinite = 1;
 }
 
-// dz = dy * act'(y) from the epilogue's OUTPUT y: ReLU (act 1) y > 0 ? dy : 0,
-// tanh (act 2) dy * (1 - y*y) (TF ReluGrad / TanhGrad, as k_bias_act_bwd)
-__device__ __forceinline__ float act_mask(float g, float v, int act) {
-#pragma clang fp contract(off)
-  return act == 2 ? g * (1.f - v * v) : (v > 0.f ? g : 0.f);
-}
-
+// dz = dy * act'(y) from the epilogue's OUTPUT y (act.h's act_grad; act is
+// CG_ACT_RELU or CG_ACT_TANH)
 __global__ __launch_bounds__(256) void k_act_bwd(const float* __restrict__ dy,
                                                  const float* __restrict__ y, int act,
                                                  float* __restrict__ dz, int64_t n) {
   for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n; i += int64_t(gridDim.x) * 256)
-    dz[i] = act_mask(dy[i], y[i], act);
+    dz[i] = act_grad(dy[i], y[i], act);
 }
 
 // the same, four elements per lane (16-byte aligned operands, n % 4 == 0)
 __global__ __launch_bounds__(256) void k_act_bwd4(const float4* __restrict__ dy,
                                                   const float4* __restrict__ y, int act,
                                                   float4* __restrict__ dz, int64_t n4) {
-  for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n4; i += int64_t(gridDim.x) * 256) {
-    const float4 g = dy[i], v = y[i];
-    dz[i] = make_float4(act_mask(g.x, v.x, act), act_mask(g.y, v.y, act), act_mask(g.z, v.z, act),
-                        act_mask(g.w, v.w, act));
-  }
+  for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n4; i += int64_t(gridDim.x) * 256)
+    dz[i] = act_grad(dy[i], y[i], act);
 }
 
-// y = act(x + bias[i % blen]) (bias NULL: no add); act 0 none, 1 ReLU, 2 tanh.
+// y = act(x + bias[i % blen]) (bias NULL: no add); act CG_ACT_*.
 // x and y may alias.
 __global__ __launch_bounds__(256) void k_bias_act_fwd(const float* __restrict__ x,
                                                       const float* __restrict__ bias, int64_t blen,
@@ -143,8 +133,8 @@ __global__ __launch_bounds__(256) void k_bias_act_fwd(const float* __restrict__ 
   for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n; i += int64_t(gridDim.x) * 256) {
     float v = x[i];
     if (bias) v = v + bias[i % blen];
-    if (act == 1) v = v > 0.f ? v : 0.f;
-    else if (act == 2) v = tanhf(v);
+    if (act == CG_ACT_RELU) v = act_relu(v);
+    else if (act == CG_ACT_TANH) v = tanhf(v);  // the library tanh, not act_tanh: this kernel's own
     y[i] = v;
   }
 }
@@ -158,8 +148,8 @@ __global__ __launch_bounds__(256) void k_bias_act_bwd(const float* __restrict__ 
   for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n; i += int64_t(gridDim.x) * 256) {
     const float g = dy[i];
     float d = g;
-    if (act == 1) d = y[i] > 0.f ? g : 0.f;
-    else if (act == 2) { const float t = y[i]; d = g * (1.f - t * t); }
+    if (act == CG_ACT_RELU) d = act_relu_grad(g, y[i]);
+    else if (act == CG_ACT_TANH) d = act_tanh_grad(g, y[i]);
     dz[i] = d;
   }
 }

@@ -28,7 +28,7 @@
 //              Gate mode (synthesis, C = 4H): a block's 128 columns are the
 //              four gates of 32 units of ONE sample, so the block owns every
 //              gate of the (vertex, unit) pairs it finishes; the accumulators
-//              go through LDS to the k_lstm_fwd gate expressions.
+//              go through LDS to lstm_gates.h's lstm_cell_fwd.
 //              EX (the residual block, cg_fres_*): the moving operand is staged
 //              as in * [mask_y > 0] (the ReLU backward, kept in dz by the first
 //              row block of each column tile), and the store is
@@ -43,6 +43,7 @@
 //              transposed and weight-gradient forms are the same kernel with
 //              other strides.  One wave runs the whole k range in order, so the
 //              weight gradient (k = the stacked rows) is bitwise reproducible.
+#include "act.h"
 #include "cg_internal.h"
 #include "lstm_gates.h"
 #include "split_bf16.h"
@@ -137,7 +138,7 @@ __global__ __launch_bounds__(256) void k_gft(GftArgs a) {
       // the MFMAs; every row block stages the whole k range of its column tile,
       // so the blocks of row 0 alone keep the masked operand
 #pragma unroll
-      for (int q = 0; q < 8; ++q) v[q] = vy[q] > 0.f ? v[q] : 0.f;
+      for (int q = 0; q < 8; ++q) v[q] = act_relu_grad(v[q], vy[q]);
       if (a.dz && blockIdx.y == 0 && sval) {
         const int k0 = ks * 16 + sh * 8;
 #pragma unroll
@@ -220,7 +221,7 @@ __global__ __launch_bounds__(256) void k_gft(GftArgs a) {
           float val = acc[r][c][q];
           if constexpr (EX) {  // residual and out read at the store's own address
             if (a.res) val = val + a.res[e];
-            if (a.relu) val = val > 0.f ? val : 0.f;
+            if (a.relu) val = act_relu(val);
             if (a.accum) val = a.out[e] + val;
           }
           if constexpr (DR == 2) val = drop_one(val, a.keep, a.seed, e, 1);
@@ -256,18 +257,14 @@ __global__ __launch_bounds__(256) void k_gft(GftArgs a) {
       if (row >= a.M || u >= H) continue;
       const float* tr = tile + rl * 129 + (tid & 31);
       const float az = tr[0] + bz, ai = tr[32] + bi, af = tr[64] + bf, ao = tr[96] + bo;
-      const float z = a.ref ? gate_tan(az) : gate_tanh(az);
-      const float gi = gate_sigmoid(ai), gf = gate_sigmoid(af);
-      const float o = a.ref ? gate_tanh(ao) : gate_sigmoid(ao);
       const int64_t e = (int64_t(n) * a.M + row) * H + u;
-      const float cp = a.c_prev ? a.c_prev[e] : 0.f;
-      const float cn = gf * cp + gi * z;   // ft * c + it * zt (lib/gconv_lstm.py:215)
-      const float hn = o * gate_tanh(cn);  // ot * tanh(new_c) (:218)
-      a.c_out[e] = cn;
-      a.h_out[e] = hn;
+      const LstmCell s = lstm_cell_fwd(
+          az, ai, af, ao, [&] { return a.c_prev ? a.c_prev[e] : 0.f; }, a.ref);
+      a.c_out[e] = s.c;
+      a.h_out[e] = s.h;
       if (a.act) {
         float* ar = a.act + (int64_t(n) * a.M + row) * 4 * H + u;
-        ar[0] = z, ar[H] = gi, ar[2 * H] = gf, ar[3 * H] = o;
+        ar[0] = s.z, ar[H] = s.i, ar[2 * H] = s.f, ar[3 * H] = s.o;
       }
     }
   }
@@ -416,7 +413,7 @@ static hipError_t launch_gft_any(const void* basis, int inverse, int N, int M, i
   a.M = M, a.Mp = int(Mp), a.C = C, a.N = N;
   int64_t ctiles = (int64_t(N) * C + kGftTile - 1) / kGftTile;
   if (g) {
-    a.gate = 1, a.H = g->H, a.ref = g->gates == 0;
+    a.gate = 1, a.H = g->H, a.ref = g->gates == CG_LSTM_GATES_REFERENCE;
     a.bias = g->bias, a.c_prev = g->c_prev, a.c_out = g->c_out, a.h_out = g->h_out, a.act = g->act;
     ctiles = int64_t(N) * ((g->H + 31) / 32);
   }

@@ -12,6 +12,8 @@
 //     z = tan, i = sigmoid, f = sigmoid, o = tanh      (CG_LSTM_GATES_REFERENCE)
 //   standard LSTM: z = tanh, o = sigmoid               (CG_LSTM_GATES_STANDARD)
 //   c' = f*c + i*z ;  h' = o * tanh(c')                (:215, :218)
+// The update and its gradient are lstm_gates.h's lstm_cell_fwd / lstm_cell_bwd
+// (the one definition); the kernels here load, sum gx + gh + bias and store.
 //
 // R = N*M rows (sample-major, vertex-minor: the [N][M][.] tensors of the
 // reference).  forget_bias is accepted by the reference cell but never used
@@ -20,26 +22,11 @@
 // Bytes per row: forward reads 8H (gx, gh) + H (c) and writes 4H (saved
 // activations) + 2H (c', h'); backward reads 4H + 3H (+H dc) and writes 4H + H.
 #include "cg_internal.h"
+#include "launch.h"
 #include "lstm_gates.h"
 
 namespace cg {
 namespace {
-
-__device__ __forceinline__ float sigmoidf_(float a) { return gate_sigmoid(a); }
-
-struct GateVals {
-  float z, i, f, o;
-};
-
-template <bool REF>
-__device__ __forceinline__ GateVals activate(float az, float ai, float af, float ao) {
-  GateVals g;
-  g.z = REF ? gate_tan(az) : gate_tanh(az);
-  g.i = sigmoidf_(ai);
-  g.f = sigmoidf_(af);
-  g.o = REF ? gate_tanh(ao) : sigmoidf_(ao);
-  return g;
-}
 
 // One thread per (row r, unit j).  Gate block q of row r lives at
 // r*4H + q*H + j, so the 64 lanes of a wave read 4 coalesced 256-B runs
@@ -69,12 +56,9 @@ __global__ __launch_bounds__(256) void k_lstm_fwd(int total, int H, const float*
       af = af + bias[2 * H + j];
       ao = ao + bias[3 * H + j];
     }
-    const GateVals g = activate<REF>(az, ai, af, ao);
-    const float cp = c ? c[e] : 0.f;
-    const float cn = g.f * cp + g.i * g.z;  // ft * c + it * zt (:215)
-    const float hn = g.o * gate_tanh(cn);   // ot * tanh(new_c) (:218)
-    c_out[e] = cn;
-    h_out[e] = hn;
+    const LstmCell g = lstm_cell_fwd(az, ai, af, ao, [&] { return c ? c[e] : 0.f; }, REF);
+    c_out[e] = g.c;
+    h_out[e] = g.h;
     if (act) {
       act[g0] = g.z;
       act[g0 + H] = g.i;
@@ -84,8 +68,7 @@ __global__ __launch_bounds__(256) void k_lstm_fwd(int total, int H, const float*
   }
 }
 
-// Reverse of k_lstm_fwd (TF autodiff of the same expressions).  dh + dh_rec
-// and dc are the gradients w.r.t. this step's h' and c' (NULL = 0); writes
+// Reverse of k_lstm_fwd (lstm_cell_bwd).  dh + dh_rec and dc are the gradients w.r.t. this step's h' and c' (NULL = 0); writes
 // the pre-activation gradients dpre [R][4H] (the dy of the x- and h-conv
 // contractions and of the bias) and dc_prev = dL/dc.
 template <bool REF>
@@ -106,24 +89,21 @@ __global__ __launch_bounds__(256) void k_lstm_bwd(int total, int H, int act_um, 
     const int as = act_um ? 1 : H;
     const float z = act[a0], i = act[a0 + as], f = act[a0 + 2 * as], o = act[a0 + 3 * as];
     const float cp = c ? c[e] : 0.f;
-    const float tc = gate_tanh(c_out[e]);
+    const float co = c_out[e];
     float dhv = dh ? dh[e] : 0.f;
     if (dh_rec) dhv = dhv + dh_rec[e];
-    float dcn = dhv * o * (1.f - tc * tc);
-    if (dc) dcn = dcn + dc[e];
-    const float d_o = dhv * tc;
-    const float d_i = dcn * z, d_z = dcn * i, d_f = dcn * cp;
-    dpre[g0] = REF ? d_z * (1.f + z * z) : d_z * (1.f - z * z);  // tan' = 1 + tan^2
-    dpre[g0 + H] = d_i * (i * (1.f - i));
-    dpre[g0 + 2 * H] = d_f * (f * (1.f - f));
-    dpre[g0 + 3 * H] = REF ? d_o * (1.f - o * o) : d_o * (o * (1.f - o));
-    if (dc_prev) dc_prev[e] = dcn * f;
+    const LstmCellGrad g = lstm_cell_bwd(z, i, f, o, cp, co, dhv, dc ? dc + e : nullptr, REF);
+    dpre[g0] = g.d[0];
+    dpre[g0 + H] = g.d[1];
+    dpre[g0 + 2 * H] = g.d[2];
+    dpre[g0 + 3 * H] = g.d[3];
+    if (dc_prev) dc_prev[e] = g.dc_prev;
   }
 }
 
 // k_lstm_bwd on unit-major act records (the sequence kernel's), four units
 // per lane: every operand moves in 16-byte accesses (H % 4 == 0, 16-byte
-// aligned operands); per element the expressions of k_lstm_bwd, bitwise
+// aligned operands); per element the same lstm_cell_bwd call as k_lstm_bwd
 template <bool REF>
 __global__ __launch_bounds__(256) void k_lstm_bwd_um4(int total4, int H, const float* __restrict__ dh,
                                                       const float* __restrict__ dh_rec,
@@ -146,20 +126,13 @@ __global__ __launch_bounds__(256) void k_lstm_bwd_um4(int total4, int H, const f
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const float4 a = *reinterpret_cast<const float4*>(act + int64_t(r) * 4 * H + 4 * (j0 + u));
-      const float z = a.x, i = a.y, f = a.z, o = a.w;
-      const float cp = (&cp4.x)[u];
-      const float tc = gate_tanh((&co4.x)[u]);
       float dhv = dh ? (&dh4.x)[u] : 0.f;
       if (dh_rec) dhv = dhv + (&dr4.x)[u];
-      float dcn = dhv * o * (1.f - tc * tc);
-      if (dc) dcn = dcn + (&dc4.x)[u];
-      const float d_o = dhv * tc;
-      const float d_i = dcn * z, d_z = dcn * i, d_f = dcn * cp;
-      dp[0][u] = REF ? d_z * (1.f + z * z) : d_z * (1.f - z * z);
-      dp[1][u] = d_i * (i * (1.f - i));
-      dp[2][u] = d_f * (f * (1.f - f));
-      dp[3][u] = REF ? d_o * (1.f - o * o) : d_o * (o * (1.f - o));
-      dcp[u] = dcn * f;
+      const LstmCellGrad g = lstm_cell_bwd(a.x, a.y, a.z, a.w, (&cp4.x)[u], (&co4.x)[u], dhv,
+                                           dc ? &dc4.x + u : nullptr, REF);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) dp[q][u] = g.d[q];
+      dcp[u] = g.dc_prev;
     }
     const int64_t g0 = int64_t(r) * 4 * H + j0;
 #pragma unroll
@@ -204,13 +177,8 @@ hipError_t launch_lstm_fwd(int gates, int64_t R, int H, const float* gx, const f
                            const float* bias, const float* c, float* c_out, float* h_out,
                            float* act, hipStream_t s) {
   const int total = int(R * H);
-  if (gates == 0)
-    hipLaunchKernelGGL(k_lstm_fwd<true>, dim3(grid1d(total)), dim3(256), 0, s, total, H, gx, gh,
-                       bias, c, c_out, h_out, act);
-  else
-    hipLaunchKernelGGL(k_lstm_fwd<false>, dim3(grid1d(total)), dim3(256), 0, s, total, H, gx, gh,
-                       bias, c, c_out, h_out, act);
-  return hipGetLastError();
+  const auto k = gates == CG_LSTM_GATES_REFERENCE ? &k_lstm_fwd<true> : &k_lstm_fwd<false>;
+  return launch(k, dim3(grid1d(total)), dim3(256), 0, s, total, H, gx, gh, bias, c, c_out, h_out, act);
 }
 
 hipError_t launch_lstm_bwd(int gates, int64_t R, int H, const float* dh, const float* dh_rec,
@@ -218,25 +186,18 @@ hipError_t launch_lstm_bwd(int gates, int64_t R, int H, const float* dh, const f
                            const float* act, const float* c, const float* c_out, float* dpre,
                            float* dc_prev, hipStream_t s, int act_um) {
   const int total = int(R * H);
+  const bool ref = gates == CG_LSTM_GATES_REFERENCE;
   auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   if (act_um && H % 4 == 0 && al(dh) && al(dh_rec) && al(dc) && al(act) && al(c) && al(c_out) &&
       al(dpre) && al(dc_prev)) {
     const int total4 = total / 4;
-    if (gates == 0)
-      hipLaunchKernelGGL(k_lstm_bwd_um4<true>, dim3(grid1d(total4)), dim3(256), 0, s, total4, H, dh,
-                         dh_rec, dc, act, c, c_out, dpre, dc_prev);
-    else
-      hipLaunchKernelGGL(k_lstm_bwd_um4<false>, dim3(grid1d(total4)), dim3(256), 0, s, total4, H, dh,
-                         dh_rec, dc, act, c, c_out, dpre, dc_prev);
-    return hipGetLastError();
+    const auto k4 = ref ? &k_lstm_bwd_um4<true> : &k_lstm_bwd_um4<false>;
+    return launch(k4, dim3(grid1d(total4)), dim3(256), 0, s, total4, H, dh, dh_rec, dc, act, c, c_out,
+                  dpre, dc_prev);
   }
-  if (gates == 0)
-    hipLaunchKernelGGL(k_lstm_bwd<true>, dim3(grid1d(total)), dim3(256), 0, s, total, H, act_um, dh,
-                       dh_rec, dc, act, c, c_out, dpre, dc_prev);
-  else
-    hipLaunchKernelGGL(k_lstm_bwd<false>, dim3(grid1d(total)), dim3(256), 0, s, total, H, act_um, dh,
-                       dh_rec, dc, act, c, c_out, dpre, dc_prev);
-  return hipGetLastError();
+  const auto k = ref ? &k_lstm_bwd<true> : &k_lstm_bwd<false>;
+  return launch(k, dim3(grid1d(total)), dim3(256), 0, s, total, H, act_um, dh, dh_rec, dc, act, c,
+                c_out, dpre, dc_prev);
 }
 
 int colsum_chunks(int64_t R) {

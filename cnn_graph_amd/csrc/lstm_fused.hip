@@ -44,8 +44,6 @@ constexpr int kQ = 8;      // channels per SpMM pass (quarter of H)
 constexpr int kSR = 12;    // LDS slot row stride (floats)
 constexpr int kWC = 64;    // gate columns per workgroup
 
-__device__ __forceinline__ float sigm(float a) { return gate_sigmoid(a); }
-
 struct HStepArgs {
   const int* rowptr;
   const int* col;
@@ -223,19 +221,17 @@ __global__ __launch_bounds__(kHT) void k_lstm_hstep(HStepArgs A) {
         af = af + A.bias[64 + j];
         ao = ao + A.bias[96 + j];
       }
-      const float z = A.gates == 0 ? gate_tan(az) : gate_tanh(az);
-      const float ig = sigm(ai), fg = sigm(af);
-      const float o = A.gates == 0 ? gate_tanh(ao) : sigm(ao);
-      const float cp = A.c_prev ? A.c_prev[rr * kH + j] : 0.f;
-      const float cn = fg * cp + ig * z;
-      A.c_out[rr * kH + j] = cn;
-      A.h_out[rr * kH + j] = o * gate_tanh(cn);
+      const LstmCell s = lstm_cell_fwd(
+          az, ai, af, ao, [&] { return A.c_prev ? A.c_prev[rr * kH + j] : 0.f; },
+          A.gates == CG_LSTM_GATES_REFERENCE);
+      A.c_out[rr * kH + j] = s.c;
+      A.h_out[rr * kH + j] = s.h;
       if (A.act) {
         float* a = A.act + rr * 128 + j;
-        a[0] = z;
-        a[32] = ig;
-        a[64] = fg;
-        a[96] = o;
+        a[0] = s.z;
+        a[32] = s.i;
+        a[64] = s.f;
+        a[96] = s.o;
       }
     }
   }

@@ -45,8 +45,8 @@
 //   the streaming k_cheb_step launches' (CG_OPT_SEQ_XPRE = 2 keeps those).
 //
 // k_lstm_bstep (backward, one launch per step, two workgroups per sample)
-//   dpre = TF autodiff of the pointwise update (the expressions of
-//   lstm.hip::k_lstm_bwd, so dpre is bitwise the unfused kernel's), then
+//   dpre = TF autodiff of the pointwise update (lstm_gates.h's lstm_cell_bwd,
+//   written out here; lstm.hip::k_lstm_bwd calls it: dpre is bitwise the same), then
 //   D_k = dpre Wh_k^T on v_mfma_f32_16x16x4_f32 (again transposed: each lane
 //   computes dpre for 8 units x 4 gates of one row and feeds it as the B
 //   operand), then the reverse (Clenshaw) recurrence over the explicit L~^T
@@ -73,8 +73,6 @@ constexpr int kBS = 16;    // channels per backward workgroup (half of H)
 constexpr int kRT = 4;     // forward: 32-row tiles per wave (8 waves x 4 x 32 = 1024 rows)
 constexpr int kRB = 8;     // backward: 16-row tiles per wave (8 x 8 x 16 = 1024 rows)
 constexpr int kSeqStaticLds = 64;  // k_lstm_seq's static __shared__ bytes (upper bound)
-
-__device__ __forceinline__ float sigm(float a) { return gate_sigmoid(a); }
 
 // agent-scope relaxed accesses: global_load/store ... sc1 (L1 bypass)
 __device__ __forceinline__ float ld_sc1(const float* p) {
@@ -626,21 +624,23 @@ __global__ __launch_bounds__(kST) void k_lstm_seq(SeqArgs A) {
               af = af + s_b[64 + u0 + m];
               ao = ao + s_b[96 + u0 + m];
             }
-            float z, ig, fg, o, cn;
+            float z, ig, fg, o;
             if (CG_DBG(A.dbg, 4)) {
               z = az;
               ig = ai;
               fg = af;
               o = ao;
-              cn = c[m] + az;
+              const float cn = c[m] + az;
               c[m] = cn;
               hn[m] = ao * cn;
             } else {
+              // lstm_gates.h's lstm_cell_fwd written out: the call made config E
+              // 1.1 % slower (profiles/r14_one_cell); held to it by test_every_cell_site_agrees_bitwise
               z = REF ? gate_tan(az) : gate_tanh(az);
-              ig = sigm(ai);
-              fg = sigm(af);
-              o = REF ? gate_tanh(ao) : sigm(ao);
-              cn = fg * c[m] + ig * z;
+              ig = gate_sigmoid(ai);
+              fg = gate_sigmoid(af);
+              o = REF ? gate_tanh(ao) : gate_sigmoid(ao);
+              const float cn = fg * c[m] + ig * z;
               c[m] = cn;
               hn[m] = o * gate_tanh(cn);
             }
@@ -827,7 +827,7 @@ __global__ __launch_bounds__(kST) void k_lstm_bstep(BStepArgs A) {
   for (int rt = 0; rt < kRB; ++rt)
 #pragma unroll
     for (int o = 0; o < K; ++o) acc[rt][o] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const bool ref = A.gates == 0;
+  const bool ref = A.gates == CG_LSTM_GATES_REFERENCE;
   const bool own = (q >> 1) == u;  // this lane's units are stored by this workgroup
   // phase A: dpre of units 8q .. 8q+7 of the lane's rows, and D_o
 #pragma unroll
@@ -875,7 +875,8 @@ __global__ __launch_bounds__(kST) void k_lstm_bstep(BStepArgs A) {
       float dcp[8];
 #pragma unroll
       for (int m = 0; m < 8; ++m) {
-        // the expressions (and their order) of lstm.hip::k_lstm_bwd
+        // lstm_gates.h's lstm_cell_bwd written out: the call costs k_lstm_bstep<2, true>
+        // two VGPRs (212 -> 214); held to it by test_every_cell_site_agrees_bitwise
         const float z = av[0][m], i = av[1][m], f = av[2][m], o = av[3][m];
         const float tc = gate_tanh(co[m]);
         float dh = A.dh ? dhv[m] : 0.f;
@@ -1207,7 +1208,7 @@ hipError_t launch_lstm_seq(int gates, int T, int N, int M, int K, int64_t nnz, c
   static constexpr decltype(&k_lstm_seq<false, false>) kerns[2][2] = {
       {&k_lstm_seq<false, false>, &k_lstm_seq<false, true>},
       {&k_lstm_seq<true, false>, &k_lstm_seq<true, true>}};
-  const auto kfn = kerns[a.xpre ? 1 : 0][gates == 0 ? 1 : 0];
+  const auto kfn = kerns[a.xpre ? 1 : 0][gates == CG_LSTM_GATES_REFERENCE ? 1 : 0];
   // the kernel's static LDS (the abort word) counts against the same 160 KB
   e = allow_big_lds(kernel_ptr(kfn), kLdsBytes - kSeqStaticLds, dev);
   if (e != hipSuccess) return e;

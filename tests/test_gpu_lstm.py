@@ -653,3 +653,113 @@ def test_layer_without_final_c(dev):
     torch.cuda.synchronize()
     for a, b in zip(grads[True], grads[False]):
         assert int(torch.count_nonzero(a)) > 0 and torch.equal(a, b)
+
+
+def _branch_point_preacts(R, C, seed):
+    """[R, C] finite pre-activations: the arguments at which gate_tan /
+    gate_tanh / gate_sigmoid change path (none of them -0), then uniform
+    draws on [-3, 3]."""
+    pi = np.float32(np.pi)
+    nxt = lambda v, d: np.nextafter(np.float32(v), np.float32(d))  # noqa: E731
+    pts = [0.6249999, 0.625, 0.6250001, pi / 4, nxt(pi / 2, 0), pi / 2, nxt(pi / 2, 4),
+           nxt(3 * pi / 2, 0), 3 * pi / 2, nxt(3 * pi / 2, 8), 10, 20, 44, 88, 8191.5, 8192, 1e4]
+    special = np.array([0.0] + [s * p for p in pts for s in (1, -1)], dtype=np.float32)
+    a = np.random.default_rng(seed).uniform(-3, 3, size=R * C).astype(np.float32)
+    # every special value once in each of the four gate blocks
+    a = a.reshape(R, 4, C // 4)
+    for q in range(4):
+        a[:len(special), q, q] = special
+        a[:len(special), q, (q + 5) % (C // 4)] = special[::-1]
+    a = a.reshape(R, C)
+    assert np.isfinite(a).all() and not np.signbit(a[a == 0]).any()
+    return a
+
+
+@pytest.mark.parametrize("gates", ["reference", "standard"])
+def test_every_cell_site_agrees_bitwise(dev, gates):
+    """The cell has one definition (lstm_gates.h); every kernel that runs it
+    gives the same bits for the same pre-activations, taken where the gate
+    functions branch.  Ring of 40 vertices, N = 3, H = 32, K = 2; zero
+    recurrent weights and zero h, so the h contribution is exactly +0.
+    Forward: lstm_cell_forward, lstm_hconv_step and lstm_seq_forward (T = 1)
+    on gx, and flstm_step against lstm_cell_forward on the pre-activations its
+    own synthesis forms from the analysis of gx (U U^T gx is gx only to
+    rounding, so the Fourier site is compared on the values it really sees).
+    Backward: lstm_cell_backward on gate-major records, aligned and from a
+    misaligned view (k_lstm_bwd); the pointwise backward on unit-major records
+    (k_lstm_bwd_um4: the library reaches it through lstm_bwd_step without an
+    h-conv, which takes 16-byte aligned operands only, so the unit-major
+    records have no misaligned case); lstm_bwd_step on both layouts."""
+    from cnn_graph_amd import filter as F
+    from cnn_graph_amd import ops
+    from cnn_graph_amd.plan import ChebPlan
+    M, N, H, K = 40, 3, 32, 2
+    idx = np.arange(M)
+    A = scipy.sparse.coo_matrix((np.full(2 * M, -0.5, np.float32),
+                                 (np.r_[idx, idx], np.r_[(idx + 1) % M, (idx - 1) % M])), shape=(M, M))
+    Lt = A.tocsr()  # L~ = L - I of the ring's normalised Laplacian (lmax = 2)
+    plan = ChebPlan(Lt, device=0)
+    gx_np = _branch_point_preacts(N * M, 4 * H, seed=7)
+    gx = t(gx_np, dev).view(N, M, 4 * H)
+    c_np = np.random.default_rng(8).standard_normal((N, M, H)).astype(np.float32)
+    c = t(c_np, dev)
+    zh = torch.zeros((N, M, H), device=dev)
+    Wh0 = torch.zeros((K * H, 4 * H), device=dev)
+
+    # forward, the three Chebyshev-side sites on gx
+    c1, h1, act = ops.lstm_cell_forward(gx, None, None, c, H, gates)
+    c2, h2, act2 = ops.lstm_hconv_step(plan, zh, c, gx, Wh0, None, K, gates)
+    act_um = torch.empty((1, N, M, 4 * H), device=dev)
+    hs, cs, _ = ops.lstm_seq_forward(plan, gx.view(1, N, M, 4 * H).contiguous(), Wh0, None, K, 1, N, gates,
+                                     h0=zh, c0=c, out_act=act_um, check=True)
+    um2gm = lambda a: a.reshape(N, M, H, 4).transpose(-1, -2).reshape(N, M, 4 * H)  # noqa: E731
+    for name, cc, hh, aa in (("hstep", c2, h2, act2), ("seq", cs[0], hs[0], um2gm(act_um))):
+        assert torch.equal(cc, c1) and torch.equal(hh, h1) and torch.equal(aa, act), name
+
+    # the Fourier site, on the pre-activations its synthesis forms
+    L = (Lt + scipy.sparse.identity(M, dtype=np.float32, format="csr")).tocsr()
+    basis = ops.gft_prepare(F.fourier_basis(L, dev))
+    ghat = ops.gft(basis, gx)
+    a_f = ops.gft(basis, ghat, inverse=True)
+    assert O.normwise_err(a_f.cpu().numpy(), gx_np.reshape(N, M, 4 * H).astype(np.float64)) < TOL
+    c3, h3, act3, _ = ops.flstm_step(basis, zh, c, ghat, torch.zeros((M, 4 * H, H), device=dev), None, gates)
+    c4, h4, act4 = ops.lstm_cell_forward(a_f, None, None, c, H, gates)
+    assert torch.equal(c3, c4) and torch.equal(h3, h4) and torch.equal(act3, act4)
+
+    # the pointwise forward against float64 from the fp32 pre-activations
+    # (rows whose |c'| stays below 1e3: tan next to its poles is unbounded)
+    a = gx_np.astype(np.float64)
+    sig = lambda v: 1 / (1 + np.exp(-v))  # noqa: E731
+    with np.errstate(over="ignore"):  # exp(1e4) = inf: the sigmoid is exactly 0 there
+        z = np.tan(a[:, :H]) if gates == "reference" else np.tanh(a[:, :H])
+        i, f = sig(a[:, H:2 * H]), sig(a[:, 2 * H:3 * H])
+        o = np.tanh(a[:, 3 * H:]) if gates == "reference" else sig(a[:, 3 * H:])
+    cn = f * c_np.reshape(-1, H).astype(np.float64) + i * z
+    keep = np.abs(cn).max(axis=1) < 1e3
+    assert keep.sum() > N * M // 2
+    for name, got, ref in (("c", c1, cn), ("h", h1, o * np.tanh(cn)),
+                           ("act", act, np.concatenate([z, i, f, o], 1))):
+        err = O.normwise_err(got.cpu().numpy().reshape(N * M, -1)[keep], ref[keep])
+        print(f"{gates} {name}: normwise err {err:.3e}")
+        assert err < TOL, (name, err)
+
+    # backward from those records and fixed dh, dc
+    g = torch.Generator(device=dev)
+    g.manual_seed(9)
+    dh, dhr, dc = (torch.randn((N, M, H), device=dev, generator=g) for _ in range(3))
+    dpre, dcp = ops.lstm_cell_backward(dh, dhr, dc, act, c, c1, H, gates)
+    um = act_um[0].contiguous()
+    buf = torch.empty(act.numel() + 1, device=dev)
+    mis = buf[1:].view_as(act)  # gate-major records 4 bytes past a 16-byte boundary
+    mis.copy_(act)
+    assert um.data_ptr() % 16 == 0 and mis.data_ptr() % 16 == 4
+    Whr = torch.randn((K * H, 4 * H), device=dev, generator=g) * 0.1
+    got = {"cell_misaligned": ops.lstm_cell_backward(dh, dhr, dc, mis, c, c1, H, gates),
+           "um4": ops.lstm_bwd_step(plan, dh, dhr, dc, um, c, c1, Whr, K, gates, act_unit_major=True,
+                                    need_dh_prev=False)[:2],
+           "bstep": ops.lstm_bwd_step(plan, dh, dhr, dc, act, c, c1, Whr, K, gates)[:2],
+           "bstep_um": ops.lstm_bwd_step(plan, dh, dhr, dc, um, c, c1, Whr, K, gates,
+                                         act_unit_major=True)[:2]}
+    torch.cuda.synchronize()
+    for name, (d, cp) in got.items():
+        assert torch.equal(d.view_as(dpre), dpre) and torch.equal(cp, dcp), name
